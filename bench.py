@@ -17,8 +17,13 @@ on every rank and the max over ranks is reported.  ``--workload clip`` is the st
 (BASELINE configs[3]): one step = a whole 1000-frame clip sharded over the ranks, with the RCCL
 broadcast of the per-clip host data and the uint8 gather to rank 0 inside the step.
 
-Prints ONE JSON line on rank 0 with the live roofline of the dominant kernel (HIP events on the
-stream the kernels run on) and, at N=1, the CPU baseline (oracle restatement on host cores).
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline figure needs: set up,
+warm up, time ``--steps`` steps (``ms_per_step`` = the milliseconds one timed step took) and, with
+``--dump-outputs DIR``, write what the last timed step returned to ``DIR/<name>.npy`` (the inputs are
+seeded, so two builds run with the same arguments can be compared output for output).  ``--full`` adds
+the live roofline of the dominant kernel (HIP events on the stream the kernels run on, then in-kernel
+stamps of the timed launches), the timing of the other conv arithmetics (``alt_precision``) and, at
+N=1, the CPU baseline (oracle restatement on host cores).
 
 Other workloads (not the headline metric):
   --workload pipeline   one step = 16 frames through DNet -> uint8 ref -> ENet(+LNet) -> uint8
@@ -90,6 +95,13 @@ def parse():
     ap.add_argument("--lanes", type=int, default=1,
                     help="execution lanes: consecutive steps replay captured graphs on this many lanes, each on its "
                          "own stream (runtime.LaneRunner); 1 = every step on one stream")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the live roofline of the dominant "
+                         "kernel (pre-pass + in-kernel stamps), the other conv arithmetics (alt_precision) and the "
+                         "CPU baseline; --no-roofline / --no-alt / --no-cpu-baseline drop single parts of it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last timed step to DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of an output above its share of 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
@@ -113,6 +125,52 @@ def make_inputs(batch, size, device, seed):
     face[:, :3, size // 2:] = 0.0                      # masked lower half (inference.py:397)
     gt = face[:, 3:].clone()
     return mel, face, gt
+
+
+DUMP_BYTES = 64 * 10 ** 6         # --dump-outputs: ceiling of the .npy payloads of one run, all ranks together
+
+
+def _flat_outputs(out, key=None):
+    """[(key, tensor)] of a step's return value, in order: a tensor, or nested tuples / lists / dicts
+    of them (DNet returns the engine's dict).  ``key`` is the dict key that leads to the tensor
+    (``<key><i>`` for the i-th tensor of a sequence under that key), None for a positional one."""
+    if isinstance(out, torch.Tensor):
+        return [(key, out)]
+    if isinstance(out, dict):
+        return [kt for k, v in out.items() for kt in _flat_outputs(v, str(k) if key is None else f"{key}_{k}")]
+    if isinstance(out, (tuple, list)):
+        flat = [kt for o in out for kt in _flat_outputs(o, key)]
+        if key is not None and len(flat) > 1:
+            flat = [(f"{k}{i}", t) for i, (k, t) in enumerate(flat)]
+        return flat
+    return []
+
+
+def dump_outputs(out, names, directory, rank, world):
+    """Write what the last timed step returned as ``directory/<name>.npy`` (``<name>_rank<r>`` when
+    world > 1): float64 stays, every other dtype becomes float32.  ``names`` (the workload's
+    ``output_names``) applies when it has one name per tensor; otherwise a tensor is named by its dict
+    key, or ``out<i>``.  An output above its share of DUMP_BYTES is written as a sample at fixed
+    indices (NumPy default_rng(0) over the flattened array, sorted), the same in every run of the same
+    arguments."""
+    import numpy as np
+    if out is None and rank != 0:      # the clip workload gathers the frames to rank 0: the other ranks hold none
+        return
+    flat = _flat_outputs(out)
+    if not flat:
+        raise RuntimeError(f"--dump-outputs: the step returned no tensors ({type(out).__name__})")
+    if len(names) != len(flat):
+        keys = [k for k, _ in flat]
+        names = [k if k is not None and keys.count(k) == 1 else f"out{i}" for i, k in enumerate(keys)]
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // (world * len(flat)) - 1024      # 1024: room for the file's .npy header
+    for name, (_, t) in zip(names, flat):
+        a = t.detach().cpu().contiguous().numpy()
+        dt = np.float64 if a.dtype == np.float64 else np.float32
+        n = share // np.dtype(dt).itemsize
+        if a.size > n:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, n))]
+        np.save(os.path.join(directory, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a.astype(dt))
 
 
 def live_roofline(forward, workload="lipsync"):
@@ -465,6 +523,8 @@ class SelfTest(Workload):
 
 
 class LipSync(Workload):
+    output_names = ("out", "low")      # ENet's enhanced frames and LNet's low-resolution frames (ENet.py:139)
+
     def __init__(self, args, dev, rank, world=1):
         from s2v_amd import models, synth
         from s2v_amd.models import arch
@@ -951,6 +1011,8 @@ def main():
     args = parse()
     if args.device == "cpu" and args.workload != "selftest":
         raise SystemExit("--device cpu runs only the launcher self-test (--workload selftest)")
+    if args.dump_stamps and (not args.full or args.no_roofline):
+        raise SystemExit("--dump-stamps needs the stamped roofline run: add --full (without --no-roofline)")
     if "WORLD_SIZE" in os.environ:                 # torchrun (the driver's N > 1 launch)
         if int(os.environ["WORLD_SIZE"]) != args.gpus:
             print(f"bench: --gpus {args.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']}; using WORLD_SIZE",
@@ -1005,6 +1067,8 @@ def worker(args):
         finally:
             ops.STAMP = None
 
+    last = {}                  # "out": what the newest timed step returned (--dump-outputs)
+
     def timed(prec, stamper=None):
         """Capture (or not) the step in conv arithmetic ``prec``, warm up, time args.steps steps
         between barriers; returns the max over ranks of the elapsed seconds."""
@@ -1028,7 +1092,7 @@ def worker(args):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last["out"] = step()
         barrier()
         el = time.perf_counter() - t0
         if world > 1:
@@ -1041,8 +1105,10 @@ def worker(args):
     # algorithmic FLOPs per launch and its isolated duration; the timed run below then stamps that
     # kernel's launches in-kernel, so the reported duration is the one of the benchmarked,
     # graph-replayed, overlapped launches (what rocprofv3 --kernel-trace sees for the same command)
+    # (--full only: a plain run sets up, warms up, times its steps and prints the result line)
+    roofline = args.full and not args.no_roofline
     pre, stamper = None, None
-    if rank == 0 and not args.no_roofline and cuda and wl.graphable:
+    if rank == 0 and roofline and cuda and wl.graphable:
         ops.set_precision(args.precision)
         pre = live_roofline(wl.forward, args.workload)
         if not args.no_graph:
@@ -1055,6 +1121,8 @@ def worker(args):
                 kern[pre["kernel"].replace("conv_igemm_x3<", "conv_igemm_x3_persist<")] = ks[pre["kernel"]] + 4
             stamper = Stamper(kern, args.warmup + args.steps + 2 * args.lanes + 4, dev)
     elapsed = timed(args.precision, stamper)
+    if args.dump_outputs:
+        dump_outputs(last.get("out"), getattr(wl, "output_names", ()), args.dump_outputs, rank, world)
     if args.dump_stamps and stamper is not None:
         with open(args.dump_stamps, "w") as f:
             json.dump({"clock_hz": Stamper.CLOCK_HZ, "kernel": pre["kernel"], "launches": stamper.raw()}, f)
@@ -1091,11 +1159,11 @@ def worker(args):
                 f"the style encoder's launches of the 256x256 tile (beside LNet) run as {_enet.style_grid(dev)} "
                 "persistent blocks on half the CUs (conv_igemm_x3_persist, s2v_conv_params.grid_cap): reported "
                 "separately under by_kernel; the headline entry is the full-grid launches only")
-    elif rank == 0 and not args.no_roofline and cuda:
+    elif rank == 0 and roofline and cuda:
         result["roofline"] = live_roofline(wl.forward, args.workload)
         for k in ("per_kernel", "_grids", "_workload"):
             result["roofline"].pop(k, None)
-    if world == 1 and not args.no_alt and cuda and wl.graphable:
+    if world == 1 and args.full and not args.no_alt and cuda and wl.graphable:
         result["alt_precision"] = {}
         for other in ARITH:
             if other == args.precision:
@@ -1104,7 +1172,7 @@ def worker(args):
             result["alt_precision"][other] = {"value": round(units / el, 3),
                                               "ms_per_step": round(1e3 * el / args.steps, 3)}
         ops.set_precision(args.precision)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and cuda:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and cuda:
         result["cpu_baseline"] = wl.cpu(args.cpu_threads or host_threads(), args.cpu_seconds)
     if rank == 0:
         print(json.dumps(result), flush=True)

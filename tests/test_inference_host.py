@@ -5,13 +5,14 @@ the synthetic frames."""
 import os
 
 import numpy as np
-import pytest
 
 import s2v_import  # noqa: F401
 from helpers import write_mp4_header, write_wav
+from conftest import GOLDEN
 from s2v_amd import inference
 
-EXAMPLES = "/root/reference/examples"
+# the reference's examples/face/1.mp4 and examples/audio/1.wav, stored unchanged as fixtures
+EXAMPLES = os.path.join(GOLDEN, "examples")
 
 
 def test_load_wav_resamples_and_downmixes(tmp_path):
@@ -43,9 +44,8 @@ def test_mp4_header_reader(tmp_path):
     assert abs(info["fps"] - 135 * 12800 / 69120) < 1e-9
 
 
-@pytest.mark.skipif(not os.path.isdir(EXAMPLES), reason="reference examples only in the build container")
 def test_reference_examples_headers():
-    info = inference.mp4_video_info(os.path.join(EXAMPLES, "face/1.mp4"))
+    info = inference.mp4_video_info(os.path.join(EXAMPLES, "face_1.mp4"))
     assert (info["width"], info["height"], info["frames"]) == (700, 700, 135)
-    x = inference.load_wav(os.path.join(EXAMPLES, "audio/1.wav"), 16000)
+    x = inference.load_wav(os.path.join(EXAMPLES, "audio_1.wav"), 16000)
     assert abs(len(x) / 16000 - 221184 / 44100) < 1e-3

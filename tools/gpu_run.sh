@@ -23,6 +23,6 @@ if [ -n "$PY" ]; then
 fi
 for item in $BENCH; do
   w=${item%%:*}; extra=""; [ "$item" != "$w" ] && extra=${item#*:}; extra=${extra//,/ }
-  timeout -k 10 600 python -u bench.py --workload $w $extra > "$OUT/bench_$w.log" 2>&1 || { echo "BENCH $w FAIL"; tail -20 "$OUT/bench_$w.log"; exit 1; }
+  timeout -k 10 600 python -u bench.py --full --workload $w $extra > "$OUT/bench_$w.log" 2>&1 || { echo "BENCH $w FAIL"; tail -20 "$OUT/bench_$w.log"; exit 1; }
   tail -1 "$OUT/bench_$w.log" | cut -c1-${CUT:-1500}
 done

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The headline roofline's in-kernel stamps against rocprofv3's kernel trace of the SAME process
-(VERDICT r04 item 2): bench.py --dump-stamps under rocprofv3 --kernel-trace.
+(VERDICT r04 item 2): bench.py --full --dump-stamps under rocprofv3 --kernel-trace.
 
 For every launch of the dominant symbol's headline shape (its FLOPs per launch), in launch order, the
 trace's (start, end) and the stamps' (first block start, last block end, s_memrealtime 100 MHz) are paired;
