@@ -405,6 +405,32 @@ __device__ __forceinline__ void load_b(const ConvArgs &a, const float *__restric
     }
 }
 
+// Quad epilogue arithmetic with the rounding of every step written out: where the compiler sees
+// a * b and + c together it contracts them to one fma, so whether a step rounds once or twice
+// would otherwise depend on which loop it was compiled into.  mul4 / add4 / axpy4 round each
+// operation on its own, fma4 rounds once.
+__device__ __forceinline__ f4 mul4(f4 a, f4 b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ f4 add4(f4 a, f4 b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ f4 axpy4(f4 v, float w, float p) {   // v + (w * p), two roundings
+#pragma clang fp contract(off)
+    const float t = w * p;
+    return v + t;
+}
+__device__ __forceinline__ f4 fma4(f4 a, f4 b, f4 c) {
+    return f4{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y), __builtin_fmaf(a.z, b.z, c.z),
+              __builtin_fmaf(a.w, b.w, c.w)};
+}
+template <int I>
+struct IntC {
+    static constexpr int value = I;
+};
+
 // Epilogue of one BM x BN output tile.  The accumulators are staged through LDS (``Cs``, at least
 // CH*(BN+4) floats) CH rows at a time by ``stage(Cs, c0)`` (rows [c0, c0 + CH) of the tile, static
 // register indices), then every thread walks the chunk row by row (consecutive threads ->
@@ -457,102 +483,233 @@ __device__ __forceinline__ void epilogue_tile_map(const ConvArgs &a, float *Cs, 
     if (vq && liveq && e.shift) sh4 = *(const f4 *)(e.shift + nq);
     f4 dsb4 = {0.f, 0.f, 0.f, 0.f};
     if (EXTRA && vq && liveq && e.dup_src && e.dup_bias) dsb4 = *(const f4 *)(e.dup_bias + nq);
+    // The quad paths take the per-pixel operand (pix_add: one float per output pixel, shared by every
+    // channel quad of a row) from the four padding floats of the row's Cs line instead of loading it
+    // row by row: a dependent global load per row, and the wait for the previous row's store that
+    // comes with it (loads and stores retire in issue order), left the store loops latency-bound.
+    // One load per (row, parity class) is issued before the chunk is staged and written beside it; a
+    // dense output uses pad 0, a depth-to-space output pad cls (the upsampled pixel of each class).
+    const bool pixq = vq && e.pix_add;
+    constexpr int NPR = (4 * CH + NT - 1) / NT;
+    const float *pixb = nullptr;
+    if (pixq) pixb = e.pix_add + (long long)bidx * (a.y_step > 1 ? a.y_h : a.oh) * (a.y_step > 1 ? a.y_w : a.ow) * a.n;
+    // chunks(body): stage the tile chunk by chunk and run body(clim, cb) on each.  Every epilogue form
+    // below has a chunk loop of its own, so only the row constants of the form a launch takes are kept
+    // in registers across its chunks (with one loop around all forms the compiler hoisted every form's
+    // constants above it, beside the live accumulators).
+    auto chunks = [&](auto body) __attribute__((always_inline)) {
 #pragma unroll 1
-    for (int c0 = 0; c0 < BM; c0 += CH) {
-        __syncthreads();   // operand stages (first chunk) / the previous chunk are no longer read
-        stage(Cs, c0);
-        __syncthreads();
-        const int clim = rows(c0);
-        const int cb = base(c0);
-        if (vq) {
-            if (!liveq || clim <= 0) continue;
-            const int hw = a.oh * a.ow;
-            const int rr0 = tid / TQ;
-            int m = cb + rr0;
-            int img = m / hw, rem = m - img * hw;
-            auto act4 = [&](f4 v) {
-                v.x = fast_act(v.x, e.act, slope); v.y = fast_act(v.y, e.act, slope);
-                v.z = fast_act(v.z, e.act, slope); v.w = fast_act(v.w, e.act, slope);
-                return v;
-            };
-            if (a.y_step > 1) {
-                // strided / depth-to-space output: quads stay inside one parity class (d2s_c % 4 == 0)
+        for (int c0 = 0; c0 < BM; c0 += CH) {
+            const int clim = rows(c0);
+            const int cb = base(c0);
+            // the thread index as the compiler cannot trace it: what the chunk derives from it is worked out
+            // again for every chunk (a few instructions) and not kept in registers across the staging, where
+            // the accumulators are all live
+            // (likewise the divisors: their reciprocals are worked out where a chunk divides)
+            int tp = tid, tb = tid, hw = a.oh * a.ow, ow = a.ow;
+            asm volatile("" : "+v"(tp), "+s"(hw), "+s"(ow));
+            float pv[NPR];
+#pragma unroll
+            for (int j = 0; j < NPR; ++j) pv[j] = 0.f;
+            if (pixq && clim > 0) {
+#pragma unroll
+                for (int j = 0; j < NPR; ++j) {
+                    // (rows past the chunk's last re-read it: every lane loads a valid address, no branch)
+                    const int idx = tp + j * NT, k = idx & 3;
+                    const int m = cb + min(idx >> 2, clim - 1);
+                    long long q = m;
+                    if (a.y_step > 1) {
+                        const int img = m / hw, rem = m - img * hw;
+                        const int oy = rem / ow, ox = rem - (rem / ow) * ow;
+                        q = ((long long)img * a.y_h + oy * a.y_step + (k >> 1)) * a.y_w + ox * a.y_step + (k & 1);
+                    }
+                    pv[j] = pixb[q];
+                }
+            }
+            __syncthreads();   // operand stages (first chunk) / the previous chunk are no longer read
+            stage(Cs, c0);
+            if (pixq && clim > 0) {
+#pragma unroll
+                for (int j = 0; j < NPR; ++j) {
+                    const int idx = tp + j * NT;
+                    if (idx < 4 * CH) Cs[(idx >> 2) * LDC + BN + (idx & 3)] = pv[j];
+                }
+            }
+            __syncthreads();
+            asm volatile("" : "+v"(tb), "+s"(hw), "+s"(ow));
+            body(clim, cb, tb, hw, ow);
+        }
+    };
+    if (vq) {
+        // the per-channel vectors are waited for here: a wait for them inside the chunk loop would also
+        // wait for the stores of the chunk before (loads and stores retire in issue order)
+        asm volatile("" ::"v"(sc4), "v"(sh4));
+        if constexpr (EXTRA) asm volatile("" ::"v"(dsb4));
+        auto act4 = [&](f4 v) {
+            v.x = fast_act(v.x, e.act, slope); v.y = fast_act(v.y, e.act, slope);
+            v.z = fast_act(v.z, e.act, slope); v.w = fast_act(v.w, e.act, slope);
+            return v;
+        };
+        auto lrelu4 = [&](f4 v) {      // none / ReLU / LeakyReLU: one select per element, no call
+            v.x = v.x >= 0.f ? v.x : v.x * slope; v.y = v.y >= 0.f ? v.y : v.y * slope;
+            v.z = v.z >= 0.f ? v.z : v.z * slope; v.w = v.w >= 0.f ? v.w : v.w * slope;
+            return v;
+        };
+        // the common launches (scale, shift, noise, none / ReLU / LeakyReLU) run a row loop with no
+        // global load in it, so their stores never wait; the rest keep a loop with loads
+        const bool plain = e.act <= S2V_ACT_LRELU && !e.nc_scale && !e.res && !extra;
+        const f4 zero4 = {0.f, 0.f, 0.f, 0.f};
+        if (a.y_step > 1) {
+            // strided / depth-to-space output: quads stay inside one parity class (d2s_c % 4 == 0)
+            const int ys = a.y_step;
+            // element offset of the row's output pixel, advanced by adds: RS4 pixels along x, the
+            // row wrap and the image wrap (no multiply per row)
+            const long long q_x = (long long)RS4 * ys * a.ycs;
+            const long long q_wx = ((long long)a.y_w - a.ow) * ys * a.ycs;
+            const long long q_wy = ((long long)a.y_h - (long long)a.oh * ys) * a.y_w * a.ycs;
+            auto d2s_rows = [&](int clim, int cb, int t, int hw, int ow, auto form) __attribute__((always_inline)) {
+                constexpr int FORM = decltype(form)::value;    // 0: plain, 1: plain, res_after set, 2: generic
+                const int rr0 = t / TQ, cq = t % TQ, nq = n0 + 4 * cq;
                 const int cls = a.d2s_c > 0 ? nq / a.d2s_c : 0;
                 const int oc = a.d2s_c > 0 ? nq - cls * a.d2s_c : nq;
-                const int dy = cls >> 1, dx = cls & 1, ys = a.y_step;
-                int oy = rem / a.ow, ox = rem - (rem / a.ow) * a.ow;
+                const int dy = cls >> 1, dx = cls & 1;
                 float *__restrict__ yb = a.y + (long long)bidx * a.y_bs + oc;
-                const float *pix = e.pix_add ? e.pix_add + (long long)bidx * a.y_h * a.y_w * a.n : nullptr;
                 const float *rsrc = e.res ? e.res + (long long)bidx * a.res_bs + oc : nullptr;
+                const int m = cb + rr0;
+                const int img = m / hw, rem = m - img * hw;
+                int oy = rem / ow, ox = rem - (rem / ow) * ow;
+                const float *cp = Cs + rr0 * LDC + 4 * cq;      // the thread's quad of its current row
+                const float *pp = Cs + rr0 * LDC + BN + cls;    // ... and the row's noise value
+                long long qo = (((long long)img * a.y_h + oy * ys + dy) * a.y_w + ox * ys + dx) * a.ycs;
 #pragma unroll 1
                 for (int rr = rr0; rr < clim; rr += RS4) {
-                    const long long q = ((long long)img * a.y_h + oy * ys + dy) * a.y_w + ox * ys + dx;
+                    f4 v = fma4(*(const f4 *)cp, sc4, sh4);
+                    if (pixq) v = axpy4(v, e.pix_w, *pp);
+                    if (FORM == 2) {
+                        f4 rv = zero4;
+                        if (rsrc) rv = *(const f4 *)(rsrc + qo);
+                        if (!e.res_after) v = add4(v, rv);
+                        v = act4(v);
+                        if (e.res_after) v = add4(v, rv);
+                    } else {
+                        // (the zero added where the residual would go keeps -0.0 results as they were)
+                        if (FORM == 0) v = add4(v, zero4);
+                        v = lrelu4(v);
+                        if (FORM == 1) v = add4(v, zero4);
+                    }
+                    *(f4 *)(yb + qo) = v;
+                    cp += RS4 * LDC;
+                    pp += RS4 * LDC;
+                    qo += q_x;
                     ox += RS4;
                     while (ox >= a.ow) {
                         ox -= a.ow;
-                        if (++oy == a.oh) { oy = 0; ++img; }
+                        qo += q_wx;
+                        if (++oy == a.oh) { oy = 0; qo += q_wy; }
                     }
-                    f4 v = *(const f4 *)&Cs[rr * LDC + 4 * cq] * sc4 + sh4;
-                    if (pix) v += e.pix_w * pix[q];
-                    f4 rv = {0.f, 0.f, 0.f, 0.f};
-                    if (rsrc) rv = *(const f4 *)(rsrc + q * a.ycs);
-                    if (!e.res_after) v += rv;
-                    v = act4(v);
-                    if (e.res_after) v += rv;
-                    *(f4 *)(yb + q * a.ycs) = v;
                 }
+            };
+            if (plain) {
+                chunks([&](int clim, int cb, int t, int hw, int ow) __attribute__((always_inline)) {
+                    if (!liveq || clim <= 0) return;
+                    if (e.res_after) d2s_rows(clim, cb, t, hw, ow, IntC<1>{});
+                    else d2s_rows(clim, cb, t, hw, ow, IntC<0>{});
+                });
             } else {
-                float *__restrict__ yb = a.y + (long long)bidx * a.y_bs + nq;
-                const float *pix = e.pix_add ? e.pix_add + (long long)bidx * a.oh * a.ow * a.n : nullptr;
-                const float *rsrc = e.res ? e.res + (long long)bidx * a.res_bs + nq : nullptr;
-#pragma unroll 1
-                for (int rr = rr0; rr < clim; rr += RS4, m += RS4, rem += RS4) {
-                    while (rem >= hw) { rem -= hw; ++img; }
-                    f4 v = *(const f4 *)&Cs[rr * LDC + 4 * cq] * sc4;
-                    if (e.nc_scale) v *= *(const f4 *)(e.nc_scale + (long long)img * e.nc_ns + nq);
-                    v += sh4;
-                    if (pix) v += e.pix_w * pix[m];
-                    f4 rv = {0.f, 0.f, 0.f, 0.f};
-                    if (rsrc) rv = *(const f4 *)(rsrc + (long long)m * e.res_cs);
-                    if (!e.res_after) v += rv;
-                    v = act4(v);
-                    if (e.res_after) v += rv;
-                    if (EXTRA && e.post_mul && nq >= e.post_c0) {
-                        const long long q = (long long)m * e.post_cs + nq - e.post_c0;
-                        v = v * *(const f4 *)(e.post_mul + q) + *(const f4 *)(e.post_add + q);
-                    }
-                    *(f4 *)(yb + (long long)m * a.ycs) = v;
-                    if (EXTRA && e.dup_src) {
-                        f4 d = e.dup_a * *(const f4 *)(e.dup_src + (long long)m * e.dup_cs + nq) + dsb4;
-                        *(f4 *)(yb + (long long)m * a.ycs + e.dup_off) = act4(d);
-                    }
-                }
+                chunks([&](int clim, int cb, int t, int hw, int ow) __attribute__((always_inline)) {
+                    if (liveq && clim > 0) d2s_rows(clim, cb, t, hw, ow, IntC<2>{});
+                });
             }
-            continue;
+        } else {
+            auto plain_rows = [&](int clim, int cb, int t, auto form) __attribute__((always_inline)) {
+                constexpr int FORM = decltype(form)::value;    // 0: plain, 1: plain, res_after set
+                const int rr0 = t / TQ, cq = t % TQ, nq = n0 + 4 * cq;
+                float *__restrict__ yb = a.y + (long long)bidx * a.y_bs + nq;
+                const float *cp = Cs + rr0 * LDC + 4 * cq;      // the thread's quad of its current row
+                const float *pp = Cs + rr0 * LDC + BN;          // ... and the row's noise value
+                float *yp = yb + (long long)(cb + rr0) * a.ycs;
+                const long long y_r = (long long)RS4 * a.ycs;
+#pragma unroll 1
+                for (int rr = rr0; rr < clim; rr += RS4, cp += RS4 * LDC, pp += RS4 * LDC, yp += y_r) {
+                    f4 v = add4(mul4(*(const f4 *)cp, sc4), sh4);
+                    if (pixq) v = axpy4(v, e.pix_w, *pp);
+                    if (FORM == 0) v = add4(v, zero4);
+                    v = lrelu4(v);
+                    if (FORM == 1) v = add4(v, zero4);
+                    *(f4 *)yp = v;
+                }
+            };
+            if (plain) {
+                chunks([&](int clim, int cb, int t, int hw, int ow) __attribute__((always_inline)) {
+                    if (!liveq || clim <= 0) return;
+                    if (e.res_after) plain_rows(clim, cb, t, IntC<1>{});
+                    else plain_rows(clim, cb, t, IntC<0>{});
+                });
+            } else {
+                // per-(image, channel) scale, residual, SFT / second output, the other activations: a row
+                // loop with loads (the residual quad of a row is loaded in that row's iteration)
+                chunks([&](int clim, int cb, int t, int hw, int ow) __attribute__((always_inline)) {
+                    if (!liveq || clim <= 0) return;
+                    const int rr0 = t / TQ, cq = t % TQ, nq = n0 + 4 * cq;
+                    float *__restrict__ yb = a.y + (long long)bidx * a.y_bs + nq;
+                    const float *rsrc = e.res ? e.res + (long long)bidx * a.res_bs + nq : nullptr;
+                    int m = cb + rr0;
+                    int img = m / hw, rem = m - img * hw;
+                    const float *cp = Cs + rr0 * LDC + 4 * cq;
+                    const float *pp = Cs + rr0 * LDC + BN;
+#pragma unroll 1
+                    for (int rr = rr0; rr < clim; rr += RS4, m += RS4, rem += RS4, cp += RS4 * LDC, pp += RS4 * LDC) {
+                        while (rem >= hw) { rem -= hw; ++img; }
+                        f4 v = mul4(*(const f4 *)cp, sc4);
+                        if (e.nc_scale) v = mul4(v, *(const f4 *)(e.nc_scale + (long long)img * e.nc_ns + nq));
+                        v = add4(v, sh4);
+                        if (pixq) v = axpy4(v, e.pix_w, *pp);
+                        f4 rv = zero4;
+                        if (rsrc) rv = *(const f4 *)(rsrc + (long long)m * e.res_cs);
+                        if (!e.res_after) v = add4(v, rv);
+                        v = act4(v);
+                        if (e.res_after) v = add4(v, rv);
+                        if (EXTRA && e.post_mul && nq >= e.post_c0) {
+                            const long long q = (long long)m * e.post_cs + nq - e.post_c0;
+                            v = fma4(v, *(const f4 *)(e.post_mul + q), *(const f4 *)(e.post_add + q));
+                        }
+                        *(f4 *)(yb + (long long)m * a.ycs) = v;
+                        if (EXTRA && e.dup_src) {
+                            const f4 da = {e.dup_a, e.dup_a, e.dup_a, e.dup_a};
+                            f4 d = fma4(da, *(const f4 *)(e.dup_src + (long long)m * e.dup_cs + nq), dsb4);
+                            *(f4 *)(yb + (long long)m * a.ycs + e.dup_off) = act4(d);
+                        }
+                    }
+                });
+            }
         }
-        if (!live || clim <= 0) continue;
+        return;
+    }
+    chunks([&](int clim, int cb, int t, int hw, int ow) __attribute__((always_inline)) {
+        if (!live || clim <= 0) return;
+        const int cn = t % TPR, n = n0 + cn;     // (as outside, worked out again per chunk)
         if (a.pool) {
             // 2x2 average of the activated outputs (ResBlock: lrelu(conv1) then bilinear x0.5 ==
             // the quad mean, base_blocks.py:40-49); rows 4r..4r+3 of the chunk are one quad
             float *__restrict__ yb = a.y + (long long)bidx * a.y_bs + n;
 #pragma unroll 1
-            for (int rq = tid / TPR; 4 * rq < clim; rq += RSTEP) {
+            for (int rq = t / TPR; 4 * rq < clim; rq += RSTEP) {
                 float v = 0.f;
 #pragma unroll
                 for (int d = 0; d < 4; ++d) v += fast_act(Cs[(4 * rq + d) * LDC + cn] * sc + sh, e.act, slope);
                 yb[(long long)(cb / 4 + rq) * a.ycs] = 0.25f * v;
             }
-            continue;
+            return;
         }
         if (a.splits > 1) {
             float *w = a.ws + (long long)bz * a.M * a.cout;
 #pragma unroll 1
-            for (int rr = tid / TPR; rr < clim; rr += RSTEP)
+            for (int rr = t / TPR; rr < clim; rr += RSTEP)
                 w[(long long)(cb + rr) * a.cout + n] = Cs[rr * LDC + cn];
         } else if (simple && a.y_step <= 1) {
             float *__restrict__ yb = a.y + (long long)bidx * a.y_bs + out_col(a, n);
             const float *rsrc = e.res ? e.res + (long long)bidx * a.res_bs + n : nullptr;
-            int rr0 = tid / TPR;
+            int rr0 = t / TPR;
             if (rsrc && a.y_step <= 1) {
                 // residual rows: four loads in flight before their adds (a dependent load per
                 // row left the store loop latency-bound)
@@ -609,7 +766,7 @@ __device__ __forceinline__ void epilogue_tile_map(const ConvArgs &a, float *Cs, 
             const int oc = a.d2s_c > 0 ? n - cls * a.d2s_c : n;
             const int dy = cls >> 1, dx = cls & 1, ys = a.y_step;
             const int hw = a.oh * a.ow;
-            int m = cb + tid / TPR;
+            int m = cb + t / TPR;
             int img = m / hw, rem = m - img * hw;
             int oy = rem / a.ow, ox = rem - (rem / a.ow) * a.ow;
             float *__restrict__ yb = a.y + (long long)bidx * a.y_bs + oc;
@@ -624,7 +781,7 @@ __device__ __forceinline__ void epilogue_tile_map(const ConvArgs &a, float *Cs, 
                 }
                 return q;
             };
-            int rr = tid / TPR;
+            int rr = t / TPR;
 #pragma unroll 1
             for (; rr + 3 * RSTEP < clim; rr += 4 * RSTEP) {
                 long long q[4];
@@ -661,7 +818,7 @@ __device__ __forceinline__ void epilogue_tile_map(const ConvArgs &a, float *Cs, 
             // demod scale + noise): the row's image index advances incrementally instead of a division per
             // element (store_epilogue), which made the epilogue as long as the main loop of a 64-channel tile
             const int hw = a.oh * a.ow;
-            const int rr0 = tid / TPR;
+            const int rr0 = t / TPR;
             int m = cb + rr0;
             int img = m / hw, rem = m - img * hw;
             float *__restrict__ yb = a.y + (long long)bidx * a.y_bs + out_col(a, n);
@@ -707,9 +864,9 @@ __device__ __forceinline__ void epilogue_tile_map(const ConvArgs &a, float *Cs, 
             }
         } else {
 #pragma unroll 1
-            for (int rr = tid / TPR; rr < clim; rr += RSTEP) store_epilogue<EXTRA>(a, bidx, cb + rr, n, Cs[rr * LDC + cn]);
+            for (int rr = t / TPR; rr < clim; rr += RSTEP) store_epilogue<EXTRA>(a, bidx, cb + rr, n, Cs[rr * LDC + cn]);
         }
-    }
+    });
 }
 
 // 32x32 MFMA accumulators (C/D map: lane owns column li of each tile, rows (r&3) + 8(r>>2) + 4 lh)

@@ -657,6 +657,12 @@ __device__ __forceinline__ void conv_x3_tile(const ConvArgs &a, int L, int gx, i
                     for (int r = 0; r < 4; ++r) bad |= !__builtin_isfinite(acc4[i][j][r]);
             if (bad) __hip_atomic_store(a.nonfinite, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+        // the accumulator factor applied in place, once: left in the staging code, the compiler moved part
+        // of these multiplies ahead of the chunk loop into new registers beside the accumulators
+#pragma unroll
+        for (int i = 0; i < TM16; ++i)
+#pragma unroll
+            for (int j = 0; j < TN16; ++j) acc4[i][j] *= a.acc_scale;
         epilogue_tile_fn<BM, BN, NW, CH, EXTRA>(a, (float *)smem, tid, m0, n0, bz, bidx, [&](float *Cs, int c0) {
             constexpr int LDC = BN + 4;
 #pragma unroll
@@ -667,7 +673,7 @@ __device__ __forceinline__ void conv_x3_tile(const ConvArgs &a, int L, int gx, i
                 for (int j = 0; j < TN16; ++j)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        Cs[(r0 + 4 * (lane >> 4) + r) * LDC + wn * WTN + j * 16 + l16] = acc4[i][j][r] * a.acc_scale;
+                        Cs[(r0 + 4 * (lane >> 4) + r) * LDC + wn * WTN + j * 16 + l16] = acc4[i][j][r];
             }
         });
     } else {
