@@ -528,6 +528,28 @@ int s2v_retina_decode(const float *const *heads, const int *hs, const int *ws, i
  * landms [n][P][10], priors in PriorBox order. */
 int s2v_retina_split(const float *const *heads, const int *hs, const int *ws, int cs, int im_h, int im_w, int n,
                      float *loc, float *conf, float *landms, s2v_stream_t stream);
+/* S3FD detector input (face_detection/api.py:65, detection/sfd/detect.py:59-65): n uint8 HWC frames of
+ * ``pixels`` pixels -> fp32 NHWC4 (c0 - mean[0], c1 - mean[1], c2 - mean[2], 0), the channel order
+ * reversed first when ``flip`` (images[..., ::-1]); mean: 3 host floats; y 16-byte aligned. */
+int s2v_u8_mean_nhwc4(const unsigned char *x, int n, long long pixels, const float *mean, int flip, float *y,
+                      s2v_stream_t stream);
+/* L2Norm.forward (detection/sfd/net_s3fd.py:16-19) on an NHWC fp32 map of ``pixels`` pixels:
+ * y[p][k] = x[p][k] / (sqrt(sum_k x[p][k]^2) + eps) * weight[k] in that order (eps after the sqrt).
+ * c % 4 == 0, c <= 1024; x_cs / y_cs: pixel pitches in floats (multiples of 4, >= c); x, y and the
+ * device vector weight[c] 16-byte aligned.  In place (y == x, y_cs == x_cs) is allowed. */
+int s2v_l2norm_nhwc(const float *x, long long pixels, int c, long long x_cs, const float *weight, float eps, float *y,
+                    long long y_cs, s2v_stream_t stream);
+/* S3FD batch_detect (detection/sfd/detect.py:72-92, bbox.py:111-129) over the six fused head maps of n
+ * images.  heads[l]: host array of device pointers, level l NHWC [n][hs[l]][ws[l]][cs] (cs >= 8) with
+ * channels [conf (4) | loc (4)] on level 0 (class logits (max(c0, c1, c2), c3): net_s3fd.py:124-127) and
+ * [conf (2) | loc (4)] on levels 1-5; stride 2^(l+2), prior (stride/2 + w stride, stride/2 + h stride,
+ * 4 stride, 4 stride), variances 0.1 / 0.2; boxes in pixels, unclipped.  Every position of image b
+ * whose softmax score > thresh is written to cand[b][slot] as 8 floats [position index (int bits;
+ * level-major, then row, column), x1, y1, x2, y2, score, 0, 0] at slot atomicAdd(count[b]): the order
+ * of the slots is arbitrary (the host sorts by position index).  cand: [n][max_cand][8]; max_cand must
+ * be >= the positions per image (sum of hs[l] ws[l]). */
+int s2v_s3fd_decode(const float *const *heads, const int *hs, const int *ws, int cs, int n, float thresh, float *cand,
+                    int *count, int max_cand, s2v_stream_t stream);
 /* cv2.warpAffine(src, M, (ow, oh), flags=INTER_LINEAR or INTER_AREA, BORDER_CONSTANT 0) on n HWC
  * images (dtype 0 uint8, 1 fp32, 2 fp64; pitches in elements): M = n device 2x3 fp64 forward
  * matrices, inverted on the device (invertAffineTransform); OpenCV's fixed-point source coordinates

@@ -12,8 +12,10 @@ Steps (reference file:line in brackets):
     image (no cv2 / ffmpeg), so the frames are synthetic uint8 BGR frames of that size (SURVEY.md
     §8d allows this), or an .npy [N,H,W,3] uint8 array given as --face;
   * frames truncated to the number of mel windows [inference.py:219-221];
-  * the face box: the centred square of --box_frac of the short side (the reference finds it with
-    dlib / FAN landmarks, which need packages and weights this image lacks: DESIGN.md §7);
+  * the face box: by default the centred square of --box_frac of the short side; with --face_det the
+    reference's face_detect [inference.py:357, futils/inference_utils.py:110-148] on the device
+    (s2v_amd.face_detection: S3FD on every frame in batches of --face_det_batch_size, --pads, clamping,
+    the 5-frame smoothing unless --nosmooth), giving one box per frame;
   * 3DMM coefficients: with --checkpoints holding face3d's epoch_20.pth, the built extractor
     (s2v_amd.face3d.Face3DExtractor: align_img + ReconNetWrapper('resnet50'), facing.py:100-130)
     regresses them from the frames with the box-derived 5 landmarks; otherwise they are synthetic;
@@ -209,6 +211,23 @@ def _semantic(frames_bgr: torch.Tensor, ckpt_dir, dev):
     return ext.face_3dmm_extraction(rgb, np.full((n, 68, 2), -1.0, np.float32)), kind
 
 
+def _face_detector(ckpt_dir, dev):
+    """face_detect's default detector (inference_utils.py:111-113): FaceAlignment(_2D) over S3FD with the
+    weights of <checkpoints>/s3fd.pth, or the synthetic preset without it -> (detector, weight kind)."""
+    from . import face_detection, models, synth
+    from .models.s3fd_arch import S3FDParams
+    path = os.path.join(ckpt_dir or "", "s3fd.pth")
+    if ckpt_dir and os.path.exists(path):
+        net, kind = models.load_s3fd(path), "s3fd checkpoint"
+    else:
+        net = models.S3FD()
+        net.load_state_dict(synth.s3fd_state_dict(S3FDParams()), strict=True)
+        net, kind = net.eval(), "s3fd synthetic"
+    sfd = face_detection.SFDDetector(dev, net=net)
+    return face_detection.FaceAlignment(face_detection.LandmarksType._2D, device=dev, flip_input=False,
+                                        detector=sfd), kind
+
+
 def _ref_enhancer(ckpt_dir, dev):
     """inference.py:224-226: FaceEnhancement(in_size=512, channel_multiplier=2, narrow=1, sr_scale=4,
     model='GPEN-BFR-512', use_sr=False) as a hook on the stabilised uint8 RGB references."""
@@ -233,14 +252,19 @@ def reference_hook(enh):
 
 def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_frac: float = 0.6,
         ckpt_dir: str | None = None, enhance: bool = False, device: str = "cuda", ref_enhance: bool = False,
-        ref_hook=None, restore: bool = True, restorer=None, enhancer=None):
+        ref_hook=None, restore: bool = True, restorer=None, enhancer=None, face_det: bool = False,
+        pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
     uint8 [n,2H,2W,3]: GFPGANer.enhance(ff, only_center_face=True) (``restore``; restore.GFPGANer,
     :300-301), the FaceParse mouth mask + 10-level Laplacian blend (post.MouthBlend, :302-313), then
     FaceEnhancement-2048 with SR x2 on the 2x frame (:326-327).  ``restorer`` / ``enhancer``: given
-    objects (else built from ``ckpt_dir`` as the reference builds them)."""
+    objects (else built from ``ckpt_dir`` as the reference builds them).  ``face_det``: per-frame face
+    boxes from face_detection.face_detect(frames, pads, nosmooth, jaw_correction=True,
+    face_det_batch_size) instead of the centred square; they drive the DNet crop, the paste-back, the mouth
+    blend and FaceEnhancement's bbox, and ``meta`` gains ``boxes`` / ``box_source``.  ``detector``: an
+    object with get_detections_for_batch (else S3FD from ``ckpt_dir``/s3fd.pth, or synthetic weights)."""
     from . import audio, pipeline, post, synth
     dev = torch.device(device)
     t0 = time.time()
@@ -254,11 +278,23 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     side = int(min(H, W) * box_frac)
     y1, x1 = (H - side) // 2, (W - side) // 2
     y2, x2 = y1 + side, x1 + side
+    boxes, box_source = [(y1, y2, x1, x2)] * n, None
+    if face_det:
+        from . import face_detection
+        if detector is None:
+            detector, box_source = _face_detector(ckpt_dir, dev)
+        else:
+            box_source = "given detector"
+        det = face_detection.face_detect(frames, pads=pads, nosmooth=nosmooth, jaw_correction=True,
+                                         batch_size=face_det_batch_size, detector=detector)   # inference.py:357
+        boxes = [tuple(int(v) for v in c) for _, c in det]
+        if any(b[1] <= b[0] or b[3] <= b[2] for b in boxes):
+            raise ValueError(f"face_detect: empty face box among {boxes}")
     enet, dnet, wkind = _weights(ckpt_dir)
     # DNet source: trans_image of the box crop (256x256, ToTensor + Normalize(0.5, 0.5), RGB)
     crops = torch.empty((n, 256, 256, 3), dtype=torch.uint8, device=dev)
-    for i in range(n):
-        post.resize_linear(frames[i, y1:y2, x1:x2], (256, 256), out=crops[i])
+    for i, (by1, by2, bx1, bx2) in enumerate(boxes):
+        post.resize_linear(frames[i, by1:by2, bx1:bx2], (256, 256), out=crops[i])
     src = torch.empty((n, 3, 256, 256), device=dev)
     ctx = post._ctx(dev)
     from ._lib import check
@@ -272,8 +308,8 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     preds = pipe.run(chunks[:n], src, coeffs)                                       # [n,3,384,384] uint8
     out = frames.clone()
     hwc = preds.permute(0, 2, 3, 1).contiguous()
-    for i in range(n):                                                              # inference.py:287-291
-        post.resize_linear(hwc[i], (x2 - x1, y2 - y1), out=out[i, y1:y2, x1:x2])
+    for i, (by1, by2, bx1, bx2) in enumerate(boxes):                                # inference.py:287-291
+        post.resize_linear(hwc[i], (bx2 - bx1, by2 - by1), out=out[i, by1:by2, bx1:bx2])
     enhanced = None
     if enhance:
         from . import face as faces
@@ -286,10 +322,9 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
             restorer = GFPGANer(model_path=os.path.join(base, "GFPGANv1.4.pth"), upscale=1, arch="clean",
                                 channel_multiplier=2, bg_upsampler=None, device=device, base_dir=base)   # :255-256
         mouth = post.MouthBlend(enh.faceparser)
-        box = (y1, y2, x1, x2)
         enhanced = []
         for i in range(n):
-            pp = out[i]
+            pp, box = out[i], boxes[i]
             if restore:
                 _, _, restored_img = restorer.enhance(pp, has_aligned=False, only_center_face=True,
                                                       paste_back=True)                  # inference.py:300-301
@@ -303,10 +338,13 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
             "box": [y1, y2, x1, x2], "semantic": skind, "ref_enhance": ref_hook is not None,
             "restore": bool(enhance and restore),
             "seconds": round(time.time() - t0, 3)}
+    if face_det:
+        meta["boxes"] = [list(b) for b in boxes]
+        meta["box_source"] = box_source
     return {"frames": out, "preds": preds, "enhanced": enhanced, "meta": meta}
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--face", required=True, help="MP4 (header read; synthetic frames) or uint8 [N,H,W,3] .npy")
     ap.add_argument("--audio", required=True, help="PCM .wav")
@@ -318,9 +356,21 @@ def main(argv=None):
     ap.add_argument("--enhance", action="store_true")
     ap.add_argument("--no_restore", action="store_true", help="with --enhance: skip GFPGANer + the mouth blend")
     ap.add_argument("--ref_enhance", action="store_true", help="Step 5: FaceEnhancement-512 on the references")
-    a = ap.parse_args(argv)
+    ap.add_argument("--face_det", action="store_true", help="per-frame face boxes from S3FD (face_detect)")
+    ap.add_argument("--pads", nargs="+", type=int, default=[0, 20, 0, 0],
+                    help="with --face_det: padding (top, bottom, left, right) of the detected box")
+    ap.add_argument("--nosmooth", action="store_true", help="with --face_det: no 5-frame smoothing of the boxes")
+    ap.add_argument("--face_det_batch_size", type=int, default=4, help="with --face_det: frames per detector batch")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if len(a.pads) != 4:
+        raise SystemExit("--pads takes four integers: top bottom left right")
     r = run(a.face, a.audio, a.max_frames, a.LNet_batch_size, a.box_frac, a.checkpoints, a.enhance,
-            ref_enhance=a.ref_enhance, restore=not a.no_restore)
+            ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
+            nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     arrays = {"frames": r["frames"].cpu().numpy(), "preds": r["preds"].cpu().numpy()}
     if r["enhanced"] is not None:

@@ -16,7 +16,7 @@ import torch
 
 from .. import ops
 from ..ops import NHWC
-from . import arch, enhancer_arch, face3d_arch, parse_arch, retinaface_arch, sr_arch
+from . import arch, enhancer_arch, face3d_arch, parse_arch, retinaface_arch, s3fd_arch, sr_arch
 
 
 def _fold5(x, dim):
@@ -321,6 +321,35 @@ def retina_outputs(ctx, maps, im_h, im_w):
     return loc, conf, lms
 
 
+class S3FD(_EngineMixin, s3fd_arch.S3FDParams):
+    """third_part/face_detection/detection/sfd/net_s3fd.py:22-129 (``s3fd``)."""
+
+    def _build_engine(self, sd, device):
+        from ..engine.s3fd import S3FDEngine
+        return S3FDEngine(sd, device)
+
+    def head_maps(self, x4: NHWC):
+        """x4: NHWC [B,H,W,4] fp32 (pixels minus (104, 117, 123), channel 3 zero) -> the six fused
+        [conf | loc] head maps (engine/s3fd.py) and the lane context they were computed on."""
+        s3fd_arch.level_sizes(x4.h, x4.w)
+        eng, ctx = self._engine(x4.t.device)
+        return self._guarded(ctx, lambda: eng.forward_maps(ctx, x4)), ctx
+
+    @torch.no_grad()
+    def forward(self, x):
+        """x [B,3,H,W] fp32 -> [cls1, reg1, .., cls6, reg6] (NCHW; cls1 max-outed to 2 channels)."""
+        _need_cuda(x)
+        b, c, h, w = x.shape
+        if c != 3:
+            raise RuntimeError(f"S3FD: expected 3 input channels, got {c}")
+        s3fd_arch.level_sizes(h, w)
+        eng, ctx = self._engine(x.device)
+        x4 = NHWC.empty(b, h, w, 4, x.device)
+        ops.fill(ctx, x4.t)
+        ops.nchw_to_nhwc(ctx, x.float(), x4.slice(0, 3))
+        return eng.split_heads(self._guarded(ctx, lambda: eng.forward_maps(ctx, x4)))
+
+
 class ReconNetWrapper(_EngineMixin, face3d_arch.ReconNetWrapperParams):
     """third_part/face3d/models/networks.py:66-105 with net_recon='resnet50', use_last_fc=False (the
     configuration load_face3d_net builds, futils/inference_utils.py:261-267)."""
@@ -428,6 +457,13 @@ def load_retinaface(path):
     if not set(sd) & set(net.state_dict()):
         raise AssertionError("load NONE from pretrained checkpoint")
     net.load_state_dict(sd, strict=False)
+    return net.eval()
+
+
+def load_s3fd(path):
+    """SFDDetector.__init__ (sfd_detector.py:24-29): s3fd() with the file's state_dict, strict, eval."""
+    net = S3FD()
+    net.load_state_dict(_load(path), strict=True)
     return net.eval()
 
 

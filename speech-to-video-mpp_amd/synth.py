@@ -158,6 +158,35 @@ RRDB_SYNTH = dict(gain=1.0)
 # RetinaFace-R50: 16 bottlenecks add onto the identity; gain 1.0 keeps the features O(1..10)
 RETINA_SYNTH = dict(gain=1.0)
 
+# S3FD (VGG-16 trunk, no residuals) at gain 1.0.  Hash-noise frames give every position of a level
+# nearly the same features, so the plain preset's class logits are a per-level constant plus a small
+# spread (face - background: level 0 -0.20 +- 0.04, level 1 +0.08 +- 0.03, fc7 -0.3 +- 0.6): every score
+# sits at 0.45-0.55 and all positions pass batch_detect's 0.05; gain 1.3 saturates the deep levels
+# instead (logits ~80, scores tied at 1).  So the six ``*_mbox_conf`` weights and biases are scaled per
+# level (face - background spread of 1.5 .. 4 logit units) and the face-class bias of each level is then
+# shifted: on levels 0 / 1 (most of the positions) 0.05 sits at the ~99th percentile, so only the tail
+# passes; on levels 2-5 the mean score is near 0.5 and most positions pass.  A Gaussian tail cut at a
+# threshold crowds its survivors against it; keeping the two big levels' tails short is what leaves
+# < 5 % of an image's candidates within the forward tolerance of 0.05 / 0.5.  With these values
+# (tests/golden/make_s3fd_golden.py asserts it) the conf logits have |max| 4..16 on every level, a
+# 137x181 frame has ~190 candidates, a 64x64 frame ~65, and the top scores are ~0.999.
+S3FD_SYNTH = dict(gain=1.0)
+S3FD_CONF_PREFIXES = ("conv3_3_norm", "conv4_3_norm", "conv5_3_norm", "fc7", "conv6_2", "conv7_2")
+S3FD_CONF_SCALE = (64.0, 110.0, 70.0, 3.5, 20.0, 45.0)
+S3FD_FACE_BIAS = (2.4, -19.7, 10.8, 1.6, -3.9, -6.9)      # added to the face-class (last) conf bias
+
+
+def s3fd_state_dict(module):
+    """The S3FD synthetic preset: synth_torch_state_dict(module, **S3FD_SYNTH) with the class heads
+    rescaled (S3FD_CONF_SCALE) and their face-class biases shifted (S3FD_FACE_BIAS)."""
+    sd = synth_torch_state_dict(module, **S3FD_SYNTH)
+    for prefix, scale, shift in zip(S3FD_CONF_PREFIXES, S3FD_CONF_SCALE, S3FD_FACE_BIAS):
+        w, b = f"{prefix}_mbox_conf.weight", f"{prefix}_mbox_conf.bias"
+        sd[w] = sd[w] * scale
+        sd[b] = sd[b] * scale
+        sd[b][-1] += shift
+    return sd
+
 
 # ----------------------------------------------------------------------------- inputs
 def hash_array(key: str, shape, lo: float = -1.0, hi: float = 1.0) -> np.ndarray:
