@@ -641,6 +641,37 @@ int s2v_pil_resize_crop(const unsigned char *x, int n, int h0, int w0, long long
  * (face3d models/networks.py ResNet._forward_impl avgpool). */
 int s2v_spatial_mean_nhwc(const float *x, int n, int hw, int c, float *y, s2v_stream_t stream);
 
+/* ---- FAN 68-point landmark network (third_part/face_detection/models.py:13-201, utils.py:56-170) ---- */
+
+/* FAN is pre-activation: every conv reads relu(bn(x)) while the raw x feeds the residual and the channel
+ * concat.  y[p][y_off + k] = relu(x[p][x_off + k] * scale[k] + shift[k]) for k < c on channel views of
+ * NHWC fp32 tensors (pitches x_cs / y_cs floats per pixel); c, the offsets and the pitches multiples
+ * of 4, all pointers 16-byte aligned. */
+int s2v_bn_act_nhwc(const float *x, long long pixels, int c, long long x_cs, int x_off, const float *scale,
+                    const float *shift, float *y, long long y_cs, int y_off, s2v_stream_t stream);
+/* s = a + b over [n][h][w][c] (b NULL: s = a; b_half: b is [n][h/2][w/2][c] read with nearest x2,
+ * HourGlass._forward's up1 + up2) and up to four outputs of it, each with its own pixel pitch, NULL
+ * skipped: s, sa = relu(s * scale_a + shift_a), p = the 2x2 mean of s (F.avg_pool2d(s, 2, 2),
+ * [n][h/2][w/2][c]) and pa = relu(p * scale_b + shift_b).  p, pa and b_half need even h and w. */
+int s2v_fan_merge(const float *a, long long a_cs, const float *b, long long b_cs, int b_half, int n, int h, int w,
+                  int c, float *s, long long s_cs, float *sa, long long sa_cs, const float *scale_a,
+                  const float *shift_a, float *p, long long p_cs, float *pa, long long pa_cs, const float *scale_b,
+                  const float *shift_b, s2v_stream_t stream);
+/* utils.crop (utils.py:92-129) for a batch of faces in one launch: table int32 [faces][5] = (frame,
+ * ul.x, ul.y, br.x, br.y) with ul / br as crop computes them (transform(.., invert=True)), once in
+ * device memory (table) and once on the host (host_table, validated before the launch: frame index,
+ * non-empty window).  frames: uint8 [n][h][w][3]; y: fp32 [faces][256][256][4] = the resized uint8
+ * window / 255, channel 3 zero.  The zero-filled window is never materialised; the resize is
+ * cv2.resize(INTER_LINEAR) on uint8 as s2v_resize_linear mode 0 computes it. */
+int s2v_fan_crop(const unsigned char *frames, int n, int h, int w, const int *table, const int *host_table, int faces,
+                 float *y, s2v_stream_t stream);
+/* get_preds_fromhm (utils.py:144-161) on NHWC heatmaps [n][64][64][cs] (c <= cs channels used):
+ * preds [n][c][2] = (x, y) of the first maximum (1-based), moved +-0.25 by the sign of the neighbour
+ * differences when 0 < pX < 63 and 0 < pY < 63 (a zero difference: no step), minus 0.5;
+ * vals [n][c] = the maxima. */
+int s2v_fan_peaks(const float *hm, int n, int h, int w, int c, long long cs, float *preds, float *vals,
+                  s2v_stream_t stream);
+
 const char *s2v_last_error(void);
 /* number of compute units of the current device (0 if no device) */
 int s2v_device_cus(void);

@@ -12,9 +12,10 @@ Reference chain per frame (facing.py:108-127):
 
 Here the 5-point POS fits (a 10 x 8 least-squares problem per frame) stay on the host, like NMS;
 the resize + crop of every frame runs in one s2v_pil_resize_crop launch per batch (Pillow's
-fixed-point arithmetic, bit-exact) straight into the NHWC input of the ResNet-50 engine.  The FAN
-landmark detector (the face_alignment package) is not part of the reference tree and not
-installed: landmarks are an input here, as the reference's own cache file ``*_landmarks.txt`` is.
+fixed-point arithmetic, bit-exact) straight into the NHWC input of the ResNet-50 engine.  Landmarks
+are an input of the extractor, as the reference's own cache file ``*_landmarks.txt`` is;
+KeypointExtractor (extract_kp_videos.py:15-57) produces them with face_detection.FaceAlignment's FAN
+network.
 """
 from __future__ import annotations
 
@@ -152,6 +153,51 @@ def align_img(img, lm, lm3D, mask=None, target_size=float(TARGET), rescale_facto
     out = NHWC.empty(1, size, size, 4, img.device)
     resize_crop(ctx, img.contiguous()[None], [box], out)
     return trans, out.t[0, :, :, :3], lm_new, None
+
+
+class KeypointExtractor:
+    """third_part/face3d/extract_kp_videos.py:15-57 over a face_detection.FaceAlignment with a FAN network
+    (``detector``: anything with get_landmarks_from_batch).  A frame without a face gives all -1, or the
+    previous frame's points when there are any (:30-33); ``misses`` counts the frames without a face."""
+
+    def __init__(self, detector, batch=16):
+        self.detector = detector
+        self.batch = batch
+        self.misses = 0
+
+    def _first_faces(self, images):
+        """Per frame the first face's [68, 2] points, or all -1 (:41, :50-54)."""
+        out = []
+        for s in range(0, len(images), self.batch):
+            chunk = images[s: s + self.batch]
+            if not isinstance(chunk, torch.Tensor):
+                chunk = (torch.stack(list(chunk)) if isinstance(chunk[0], torch.Tensor)
+                         else np.stack([np.asarray(im) for im in chunk]))
+            for lms in self.detector.get_landmarks_from_batch(chunk):
+                if lms is None:
+                    self.misses += 1
+                    out.append(-1. * np.ones([68, 2]))
+                else:
+                    out.append(np.asarray(lms[0]))
+        return out
+
+    def extract_keypoint(self, images, name=None, info=True):
+        """A list of frames (or one [N,H,W,3] array / device tensor) -> keypoints [N, 68, 2]; one frame
+        [H,W,3] -> [68, 2].  ``name``: also written with np.savetxt to <name without extension>.txt."""
+        many = isinstance(images, (list, tuple)) or getattr(images, "ndim", 3) == 4
+        if many:
+            keypoints = []
+            for current_kp in self._first_faces(images):
+                if np.mean(current_kp) == -1 and keypoints:
+                    keypoints.append(keypoints[-1])
+                else:
+                    keypoints.append(current_kp[None])
+            keypoints = np.concatenate(keypoints, 0)
+        else:
+            keypoints = self._first_faces([images])[0]
+        if name is not None:
+            np.savetxt(os.path.splitext(name)[0] + '.txt', keypoints.reshape(-1))
+        return keypoints
 
 
 class Face3DExtractor:

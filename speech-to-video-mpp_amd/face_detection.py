@@ -16,6 +16,13 @@ batch_detect's softmax + 0.05 threshold + prior decode over all six levels of th
 (s2v_s3fd_decode).  One device -> host copy per batch brings the per-image counts and candidate rows;
 the NMS over those few rows and the box arithmetic stay on the host, as in the reference.
 
+The 68 landmarks of a face (face_alignment's get_landmarks_from_image / get_landmarks_from_batch, which
+third_part/face3d/extract_kp_videos.py:15-57 calls) run on the device as well: utils.crop of every detected
+face of a batch in one launch (s2v_fan_crop), the FAN network (models.FAN) and get_preds_fromhm's argmax
+and quarter-pixel step (s2v_fan_peaks); one device -> host copy per batch brings the 68 heatmap points per
+face, and their map back to frame coordinates (utils.transform's float32 matrix and .int()) stays on the
+host, as the reference computes it.
+
 Per-image equivalence with the reference's batched post-processing.  batch_detect (detect.py:77-92)
 collects the UNION over the batch of the positions whose score passes 0.05 in any image, once per
 hit, and evaluates every image at every collected position; SFDDetector.detect_from_batch then runs
@@ -147,12 +154,92 @@ class SFDDetector:
         return 0
 
 
+# ----------------------------------------------------------------------------- FAN landmarks
+FAN_RESOLUTION = 256.0                  # utils.crop's default resolution: the network input side
+# The glue between the detector and the network, get_landmarks_from_image, lives in the face-alignment
+# 1.3.5 package, which is not part of the reference tree.  It adds two facts that stay parity-unpinned
+# (no reference code or fixture pins them); everything else here restates reference code:
+CENTER_Y_SHIFT = 0.12                   # the box centre is moved up by this fraction of the box height
+HEATMAP_STACK = -1                      # the last stack's heatmaps are used
+# utils.shuffle_lr's default pairs (utils.py:224-228): landmark k of a flipped face is landmark FLIP_PAIRS[k]
+FLIP_PAIRS = (16, 15, 14, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 0, 26, 25, 24, 23, 22, 21, 20, 19, 18, 17, 27, 28,
+              29, 30, 35, 34, 33, 32, 31, 45, 44, 43, 42, 47, 46, 39, 38, 37, 36, 41, 40, 54, 53, 52, 51, 50, 49, 48,
+              59, 58, 57, 56, 55, 64, 63, 62, 61, 60, 67, 66, 65)
+
+
+def transform_matrix(center, scale, resolution, invert=False) -> torch.Tensor:
+    """The 3x3 float32 matrix of utils.transform (utils.py:77-85): ``center`` a float32 tensor (x, y),
+    ``scale`` a Python float; torch.inverse when ``invert``."""
+    h = 200.0 * scale
+    t = torch.eye(3)
+    t[0, 0] = resolution / h
+    t[1, 1] = resolution / h
+    t[0, 2] = resolution * (-center[0] / h + 0.5)
+    t[1, 2] = resolution * (-center[1] / h + 0.5)
+    return torch.inverse(t) if invert else t
+
+
+def transform(point, center, scale, resolution, invert=False, matrix=None) -> torch.Tensor:
+    """utils.transform (utils.py:56-89): the point through the matrix in torch float32, truncated by
+    .int().  ``matrix``: transform_matrix(center, scale, resolution, invert) computed once for many points."""
+    t = transform_matrix(center, scale, resolution, invert) if matrix is None else matrix
+    pt = torch.ones(3)
+    pt[0] = point[0]
+    pt[1] = point[1]
+    return torch.matmul(t, pt)[0:2].int()
+
+
+def box_center_scale(d, reference_scale=195):
+    """One detector row [x1, y1, x2, y2, ...] -> (center float32 tensor, scale float): the box centre with
+    y moved up by CENTER_Y_SHIFT of the height, and (w + h) / reference_scale (sfd_detector.py:49-51)."""
+    x1, y1, x2, y2 = (float(v) for v in d[:4])
+    center = torch.tensor([x2 - (x2 - x1) / 2.0, y2 - (y2 - y1) / 2.0])
+    center[1] = center[1] - (y2 - y1) * CENTER_Y_SHIFT
+    return center, (x2 - x1 + y2 - y1) / reference_scale
+
+
+def crop_window(center, scale, resolution=FAN_RESOLUTION):
+    """utils.crop's window (utils.py:107-108): (ul.x, ul.y, br.x, br.y) ints in frame coordinates."""
+    m = transform_matrix(center, scale, resolution, True)
+    ul = transform([1, 1], center, scale, resolution, True, m)
+    br = transform([resolution, resolution], center, scale, resolution, True, m)
+    return int(ul[0]), int(ul[1]), int(br[0]), int(br[1])
+
+
+def crop_table(frame_index, centers, scales, frame_hw) -> np.ndarray:
+    """The per-face table of s2v_fan_crop: int32 [faces, 5] = (frame, ul.x, ul.y, br.x, br.y).  An empty
+    window, or one that misses the frame (where utils.crop's slice assignment fails), raises ValueError."""
+    H, W = frame_hw
+    rows = []
+    for f, c, s in zip(frame_index, centers, scales):
+        ulx, uly, brx, bry = crop_window(c, s)
+        if brx <= ulx or bry <= uly:
+            raise ValueError(f"FAN crop: empty window ul=({ulx}, {uly}) br=({brx}, {bry}) for centre "
+                             f"{[float(v) for v in c]} scale {s}")
+        if min(brx, W) <= max(ulx, 0) or min(bry, H) <= max(uly, 0):
+            raise ValueError(f"FAN crop: window ul=({ulx}, {uly}) br=({brx}, {bry}) misses the {W}x{H} frame")
+        rows.append((int(f), ulx, uly, brx, bry))
+    return np.asarray(rows, np.int32).reshape(-1, 5)
+
+
+def preds_to_image(preds, center, scale, hm_size=64) -> torch.Tensor:
+    """get_preds_fromhm's preds_orig (utils.py:163-168): each heatmap point [68, 2] through
+    transform(.., hm_size, invert=True) -> float32 [68, 2] of integer values in frame coordinates."""
+    m = transform_matrix(center, scale, hm_size, True)
+    out = torch.zeros((len(preds), 2))
+    for j in range(len(preds)):
+        out[j] = transform(preds[j], center, scale, hm_size, True, m)
+    return out
+
+
 class FaceAlignment:
-    """api.py:46-79 (the detector half: the FAN landmark network is not on the face_detect path).
-    ``detector``: an SFDDetector; without it one is built from ``path_to_detector``."""
+    """api.py:46-79, plus the landmark half of face_alignment.FaceAlignment (get_landmarks_from_image /
+    get_landmarks_from_batch) over the FAN network.  ``detector``: an SFDDetector; without it one is built
+    from ``path_to_detector``.  ``fan``: an s2v_amd.models.FAN, or ``path_to_fan`` to load one; the
+    landmark methods raise without either (nothing is downloaded)."""
 
     def __init__(self, landmarks_type, device="cuda", flip_input=False, face_detector="sfd", detector=None, *,
-                 verbose=False, path_to_detector=None):
+                 verbose=False, path_to_detector=None, fan=None, path_to_fan=None):
         if face_detector != "sfd":
             raise NotImplementedError("FaceAlignment: only the 'sfd' detector exists")
         self.device = device
@@ -161,6 +248,91 @@ class FaceAlignment:
         self.verbose = verbose
         self.face_detector = detector if detector is not None else SFDDetector(device, path_to_detector,
                                                                                         verbose=verbose)
+        if fan is None and path_to_fan:
+            if not os.path.isfile(path_to_fan):
+                raise FileNotFoundError(f"FaceAlignment: no FAN weights at {path_to_fan!r}")
+            from . import models
+            fan = models.load_fan(path_to_fan)
+        self.face_alignment_net = fan.eval() if fan is not None else None
+        # flip_input's two index tables: the column order of the flipped crop / heatmap, and the landmark pairs
+        self.flip_pairs = FLIP_PAIRS
+        self.flip_columns = None            # None: reversed (utils.flip)
+        self.fan_passes = 0                 # FAN forwards run so far
+
+    # ------------------------------------------------------------------ landmarks
+    def _flip_index(self, width, dev):
+        cols = range(width - 1, -1, -1) if self.flip_columns is None else self.flip_columns(width)
+        return torch.tensor(list(cols), dtype=torch.long, device=dev)
+
+    def _fan(self, x4: NHWC) -> NHWC:
+        self.fan_passes += 1
+        return self.face_alignment_net.heatmaps(x4)[0][HEATMAP_STACK]
+
+    def crops(self, frames: torch.Tensor, table: np.ndarray) -> NHWC:
+        """s2v_fan_crop: the 256x256 network inputs [faces, 256, 256, 4] of the table's faces."""
+        n, H, W, _ = frames.shape
+        host = np.ascontiguousarray(table, np.int32)
+        dev_table = torch.from_numpy(host).to(frames.device)
+        size = int(FAN_RESOLUTION)
+        x4 = NHWC.empty(len(host), size, size, 4, frames.device)
+        ctx = post._ctx(frames.device)
+        check(ctx.lib.s2v_fan_crop(frames.data_ptr(), n, H, W, dev_table.data_ptr(), host.ctypes.data, len(host), x4.ptr,
+                                   ctx.stream), "s2v_fan_crop")
+        return x4
+
+    def peaks(self, hm: NHWC):
+        """s2v_fan_peaks on heatmaps [faces, 64, 64, cs] -> (preds [faces, 68, 2], peak values [faces, 68])
+        float32 host tensors: one device -> host copy."""
+        from .models.fan_arch import NUM_LANDMARKS as K
+        buf = torch.empty((hm.n, K * 3), device=hm.t.device)
+        ctx = post._ctx(hm.t.device)
+        check(ctx.lib.s2v_fan_peaks(hm.ptr, hm.n, hm.h, hm.w, K, hm.cs, buf.data_ptr(), buf.data_ptr() + 4 * hm.n * K * 2,
+                                    ctx.stream), "s2v_fan_peaks")
+        host = buf.cpu().reshape(-1)
+        return host[: hm.n * K * 2].reshape(hm.n, K, 2), host[hm.n * K * 2:].reshape(hm.n, K)
+
+    @torch.no_grad()
+    def get_landmarks_from_batch(self, images, detected_faces=None):
+        """images uint8 [B,H,W,3] RGB (host or device) -> per image None, or a list with one float32
+        [68, 2] array of (x, y) frame coordinates per face, in the detector's order.  ``detected_faces``:
+        per image a list of [x1, y1, x2, y2, ...] rows (else S3FD on the channel-flipped frames, as
+        get_detections_for_batch).  Per face: centre / scale (box_center_scale), utils.crop, FAN,
+        get_preds_fromhm on the last stack (flip_input: plus the flipped pass, utils.flip), preds_orig."""
+        if self.face_alignment_net is None:
+            raise RuntimeError("FaceAlignment: no FAN network (pass fan= or path_to_fan=)")
+        t = _batch(images, self.device)
+        if detected_faces is None:
+            detected_faces = self.face_detector.detect_from_batch(t, flip=True)
+        if len(detected_faces) != t.shape[0]:
+            raise ValueError("get_landmarks_from_batch: one list of boxes per image")
+        index = [i for i, dets in enumerate(detected_faces) for _ in dets]
+        results = [None] * t.shape[0]
+        if not index:
+            return results
+        ref = self.face_detector.reference_scale
+        cs = [box_center_scale(d, ref) for dets in detected_faces for d in dets]
+        table = crop_table(index, [c for c, _ in cs], [s for _, s in cs], t.shape[1:3])
+        x4 = self.crops(t, table)
+        hm = self._fan(x4)
+        if self.flip_input:
+            # out += flip(net(flip(inp))[-1], is_label=True): columns reversed, landmark channels paired
+            dev = hm.t.device
+            xf = NHWC(x4.t.index_select(2, self._flip_index(x4.w, dev)).contiguous())
+            hf = self._fan(xf)
+            k = len(self.flip_pairs)
+            back = hf.t[..., :k].index_select(2, self._flip_index(hf.w, dev))
+            back = back.index_select(3, torch.tensor(list(self.flip_pairs), dtype=torch.long, device=dev))
+            hm = NHWC((hm.t[..., :k] + back).contiguous())
+        preds, _ = self.peaks(hm)
+        for f, (i, (c, s)) in enumerate(zip(index, cs)):
+            pts = preds_to_image(preds[f], c, s, hm.h).numpy()
+            results[i] = (results[i] or []) + [pts]
+        return results
+
+    def get_landmarks_from_image(self, image, detected_faces=None):
+        """One uint8 [H,W,3] RGB image -> None without a face, else the list of [68, 2] arrays."""
+        return self.get_landmarks_from_batch(_batch(image, self.device),
+                                             None if detected_faces is None else [detected_faces])[0]
 
     def get_detections_for_batch(self, images):
         """images uint8 [B,H,W,3] -> per image (x1, y1, x2, y2) ints of the first kept box, or None."""

@@ -19,6 +19,9 @@ Steps (reference file:line in brackets):
   * 3DMM coefficients: with --checkpoints holding face3d's epoch_20.pth, the built extractor
     (s2v_amd.face3d.Face3DExtractor: align_img + ReconNetWrapper('resnet50'), facing.py:100-130)
     regresses them from the frames with the box-derived 5 landmarks; otherwise they are synthetic;
+    with --landmarks the 68 FAN landmarks of every frame (facing.py:89-97: KeypointExtractor over S3FD +
+    FAN, weights from <checkpoints>/s3fd.pth and 2DFAN4.pth or the synthetic presets) drive align_img
+    instead of the no-landmark path;
   * DNet stabilisation of the box crop (trans_image: 256x256, [-1, 1], facing.py:177-191) with the
     coefficient windows, then ENet(LNet) on [masked crop, reference] batches of LNet_batch_size,
     clamp(0, 1) * 255 [inference.py:259-267, :393-399] (s2v_amd.pipeline.LipSyncPipeline);
@@ -188,10 +191,42 @@ LM3D_STANDIN = np.array([[-0.31, 0.29, 0.41], [0.31, 0.29, 0.41], [0.0, 0.0, 0.6
                          [0.25, -0.36, 0.44]])
 
 
-def _semantic(frames_bgr: torch.Tensor, ckpt_dir, dev):
+def _lm3d(ckpt_dir):
+    """face3d's 5-point 3D reference: BFM/similarity_Lm3D_all.mat under ``ckpt_dir``, else LM3D_STANDIN."""
+    from . import face3d
+    bfm = os.path.join(ckpt_dir or "", "BFM")
+    return face3d.load_lm3d(bfm) if os.path.exists(os.path.join(bfm, "similarity_Lm3D_all.mat")) else LM3D_STANDIN
+
+
+def _usable_landmarks(lms, H, W, lm3d):
+    """Landmarks whose align_img fit s2v_pil_resize_crop cannot compute (an empty resized frame, a
+    downscale past its 48-tap limit, sizes past int32: points that are no face, as synthetic FAN weights
+    give) -> all -1,
+    the reference's own marker of a frame without landmarks (facing.py:110-113).  Returns (landmarks,
+    number of frames rejected); nothing is dropped silently, ``meta`` reports the count."""
+    from . import face3d
+    lms = np.array(lms, np.float32)
+    rejects = 0
+    for i in range(len(lms)):
+        if np.mean(lms[i]) == -1:
+            continue
+        try:
+            with np.errstate(all="ignore"):
+                _, box, _ = face3d.align_params(W, H, face3d.frame_landmarks(lms[i], W, H, lm3d), lm3d)
+            face3d._check_scale(W, H, box[0], box[1])
+            if max(abs(v) for v in box) >= 1 << 31:          # the kernel's (w, h, left, up) are int32
+                raise OverflowError(box)
+        except (ValueError, OverflowError):                 # a degenerate fit: the scale is 0, inf or NaN
+            lms[i] = -1.0
+            rejects += 1
+    return lms, rejects
+
+
+def _semantic(frames_bgr: torch.Tensor, ckpt_dir, dev, lms=None):
     """facing.py:100-130 face_3dmm_extraction on the frames: ReconNetWrapper('resnet50') from
-    face3d_pretrain_epoch_20.pth (synthetic weights without it), the reference's no-landmark path
-    (all -1 landmarks -> lm3d positions, facing.py:110-116) since FAN is absent -> [n, 262]."""
+    face3d_pretrain_epoch_20.pth (synthetic weights without it) -> [n, 262].  ``lms``: the frames' 68
+    landmarks [n, 68, 2] (_landmarks); without them the reference's no-landmark path (all -1 landmarks ->
+    lm3d positions, facing.py:110-116)."""
     from . import face3d, models, synth
     from .models.face3d_arch import ReconNetWrapperParams
     path = os.path.join(ckpt_dir or "", "face3d_pretrain_epoch_20.pth")
@@ -203,12 +238,36 @@ def _semantic(frames_bgr: torch.Tensor, ckpt_dir, dev):
         net.load_state_dict(synth.synth_torch_state_dict(ReconNetWrapperParams(), **synth.RETINA_SYNTH))
         net = net.eval()
         kind = "synthetic"
-    bfm = os.path.join(ckpt_dir or "", "BFM")
-    lm3d = face3d.load_lm3d(bfm) if os.path.exists(os.path.join(bfm, "similarity_Lm3D_all.mat")) else LM3D_STANDIN
+    lm3d = _lm3d(ckpt_dir)
     n = frames_bgr.shape[0]
     rgb = frames_bgr[..., [2, 1, 0]].contiguous()                               # facing.py reads RGB PIL frames
     ext = face3d.Face3DExtractor(net, lm3d, dev)
-    return ext.face_3dmm_extraction(rgb, np.full((n, 68, 2), -1.0, np.float32)), kind
+    if lms is None:
+        lms = np.full((n, 68, 2), -1.0, np.float32)
+    return ext.face_3dmm_extraction(rgb, lms), kind
+
+
+def _landmarks(frames_bgr: torch.Tensor, ckpt_dir, dev, detector=None):
+    """facing.py:89-97: KeypointExtractor().extract_keypoint on the RGB frames -> (landmarks [n, 68, 2],
+    FAN weight kind, frames without a face).  FAN weights from <checkpoints>/2DFAN4.pth, or the synthetic
+    FAN_SYNTH preset without it; the boxes come from the S3FD detector of _face_detector."""
+    from . import face3d, models, synth
+    from .models.fan_arch import FANParams
+    if detector is None:
+        path = os.path.join(ckpt_dir or "", "2DFAN4.pth")
+        if ckpt_dir and os.path.exists(path):
+            fan, kind = models.load_fan(path), "2DFAN4 checkpoint"
+        else:
+            fan = models.FAN()
+            fan.load_state_dict(synth.synth_torch_state_dict(FANParams(), **synth.FAN_SYNTH), strict=True)
+            fan, kind = fan.eval(), "2DFAN4 synthetic"
+        detector, _ = _face_detector(ckpt_dir, dev)
+        detector.face_alignment_net = fan
+    else:
+        kind = "given detector"
+    kp = face3d.KeypointExtractor(detector)
+    lms = kp.extract_keypoint(frames_bgr[..., [2, 1, 0]].contiguous(), info=False)
+    return lms.astype(np.float32), kind, kp.misses
 
 
 def _face_detector(ckpt_dir, dev):
@@ -253,7 +312,8 @@ def reference_hook(enh):
 def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_frac: float = 0.6,
         ckpt_dir: str | None = None, enhance: bool = False, device: str = "cuda", ref_enhance: bool = False,
         ref_hook=None, restore: bool = True, restorer=None, enhancer=None, face_det: bool = False,
-        pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None):
+        pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None,
+        landmarks: bool = False, landmark_detector=None):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -264,7 +324,11 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     boxes from face_detection.face_detect(frames, pads, nosmooth, jaw_correction=True,
     face_det_batch_size) instead of the centred square; they drive the DNet crop, the paste-back, the mouth
     blend and FaceEnhancement's bbox, and ``meta`` gains ``boxes`` / ``box_source``.  ``detector``: an
-    object with get_detections_for_batch (else S3FD from ``ckpt_dir``/s3fd.pth, or synthetic weights)."""
+    object with get_detections_for_batch (else S3FD from ``ckpt_dir``/s3fd.pth, or synthetic weights).
+    ``landmarks``: the frames' 68 FAN landmarks (_landmarks; ``landmark_detector``: an object with
+    get_landmarks_from_batch) drive the 3DMM extraction instead of the no-landmark path; ``meta`` gains
+    ``landmarks`` (the FAN weight kind), ``landmark_misses`` (frames without a face) and ``landmark_rejects``
+    (_usable_landmarks), the result gains ``semantic`` [n, 262]."""
     from . import audio, pipeline, post, synth
     dev = torch.device(device)
     t0 = time.time()
@@ -299,7 +363,11 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     ctx = post._ctx(dev)
     from ._lib import check
     check(ctx.lib.s2v_u8_to_gan(crops.data_ptr(), n, 256, 256, src.data_ptr(), ctx.stream), "s2v_u8_to_gan")
-    semantic, skind = _semantic(frames, ckpt_dir, dev)                             # facing.py:100-130
+    lms = None
+    if landmarks:
+        lms, lkind, lmiss = _landmarks(frames, ckpt_dir, dev, landmark_detector)   # facing.py:89-97
+        lms, lrej = _usable_landmarks(lms, H, W, _lm3d(ckpt_dir))
+    semantic, skind = _semantic(frames, ckpt_dir, dev, lms)                        # facing.py:100-130
     expression = synth.hash_array("inference.expression", (64,), -1.0, 1.0)        # expression.mat is absent
     coeffs = torch.from_numpy(pipeline.dnet_coefficients(semantic, expression, False, 0, n)).to(dev)
     if ref_enhance and ref_hook is None:
@@ -341,7 +409,13 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     if face_det:
         meta["boxes"] = [list(b) for b in boxes]
         meta["box_source"] = box_source
-    return {"frames": out, "preds": preds, "enhanced": enhanced, "meta": meta}
+    res = {"frames": out, "preds": preds, "enhanced": enhanced, "meta": meta}
+    if landmarks:
+        meta["landmarks"] = lkind
+        meta["landmark_misses"] = int(lmiss)
+        meta["landmark_rejects"] = int(lrej)
+        res["semantic"] = semantic
+    return res
 
 
 def build_parser():
@@ -361,6 +435,8 @@ def build_parser():
                     help="with --face_det: padding (top, bottom, left, right) of the detected box")
     ap.add_argument("--nosmooth", action="store_true", help="with --face_det: no 5-frame smoothing of the boxes")
     ap.add_argument("--face_det_batch_size", type=int, default=4, help="with --face_det: frames per detector batch")
+    ap.add_argument("--landmarks", action="store_true",
+                    help="68 FAN landmarks per frame (S3FD + 2DFAN4) drive the 3DMM extraction")
     return ap
 
 
@@ -370,11 +446,13 @@ def main(argv=None):
         raise SystemExit("--pads takes four integers: top bottom left right")
     r = run(a.face, a.audio, a.max_frames, a.LNet_batch_size, a.box_frac, a.checkpoints, a.enhance,
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
-            nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size)
+            nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     arrays = {"frames": r["frames"].cpu().numpy(), "preds": r["preds"].cpu().numpy()}
     if r["enhanced"] is not None:
         arrays["enhanced"] = r["enhanced"].cpu().numpy()
+    if "semantic" in r:
+        arrays["semantic"] = r["semantic"]
     np.savez_compressed(a.outfile, **arrays)
     print(json.dumps(dict(r["meta"], outfile=a.outfile)))
     return 0

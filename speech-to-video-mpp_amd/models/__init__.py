@@ -16,7 +16,7 @@ import torch
 
 from .. import ops
 from ..ops import NHWC
-from . import arch, enhancer_arch, face3d_arch, parse_arch, retinaface_arch, s3fd_arch, sr_arch
+from . import arch, enhancer_arch, face3d_arch, fan_arch, parse_arch, retinaface_arch, s3fd_arch, sr_arch
 
 
 def _fold5(x, dim):
@@ -350,6 +350,35 @@ class S3FD(_EngineMixin, s3fd_arch.S3FDParams):
         return eng.split_heads(self._guarded(ctx, lambda: eng.forward_maps(ctx, x4)))
 
 
+class FAN(_EngineMixin, fan_arch.FANParams):
+    """third_part/face_detection/models.py:145-201 (2D-FAN-4 with the default num_modules=4)."""
+
+    def _build_engine(self, sd, device):
+        from ..engine.fan import FANEngine
+        return FANEngine(sd, device)
+
+    def heatmaps(self, x4: NHWC):
+        """x4: NHWC [B,H,W,4] fp32 (RGB / 255, channel 3 zero; H, W multiples of 64) -> the NHWC
+        heatmaps [B,H/4,W/4,68] of every stack (engine/fan.py) and the lane context they were computed on."""
+        fan_arch.check_input(x4.h, x4.w)
+        eng, ctx = self._engine(x4.t.device)
+        return self._guarded(ctx, lambda: eng.forward(ctx, x4)), ctx
+
+    @torch.no_grad()
+    def forward(self, x):
+        """x [B,3,H,W] fp32 -> the list of ``num_modules`` heatmap tensors [B,68,H/4,W/4]."""
+        _need_cuda(x)
+        b, c, h, w = x.shape
+        if c != 3:
+            raise RuntimeError(f"FAN: expected 3 input channels, got {c}")
+        fan_arch.check_input(h, w)
+        eng, ctx = self._engine(x.device)
+        x4 = NHWC.empty(b, h, w, 4, x.device)
+        ops.fill(ctx, x4.t)
+        ops.nchw_to_nhwc(ctx, x.float(), x4.slice(0, 3))
+        return eng.to_nchw(self._guarded(ctx, lambda: eng.forward(ctx, x4)))
+
+
 class ReconNetWrapper(_EngineMixin, face3d_arch.ReconNetWrapperParams):
     """third_part/face3d/models/networks.py:66-105 with net_recon='resnet50', use_last_fc=False (the
     configuration load_face3d_net builds, futils/inference_utils.py:261-267)."""
@@ -467,6 +496,18 @@ def load_s3fd(path):
     return net.eval()
 
 
+def load_fan(path, num_modules=4):
+    """FAN(num_modules) with the weights of ``path``: a plain state_dict or {'state_dict': ...} (the
+    face_alignment package ships a TorchScript archive; INTEGRATION.md turns it into such a file),
+    strict, eval."""
+    net = FAN(num_modules)
+    sd = _load(path)
+    if isinstance(sd, dict) and "state_dict" in sd:
+        sd = sd["state_dict"]
+    net.load_state_dict(sd, strict=True)
+    return net.eval()
+
+
 def load_face3d_net(ckpt_path, device):
     """futils/inference_utils.py:261-267: ReconNetWrapper('resnet50') with checkpoint['net_recon'],
     strict, eval, on ``device``."""
@@ -485,4 +526,4 @@ def load_srmodel(path, scale=2, num_feat=32):
 
 __all__ = ["LNet", "ENet", "DNet", "GFPGANv1Clean", "FullGenerator", "ParseNet", "RRDBNet", "load_checkpoint",
            "load_network", "load_DNet", "load_gfpgan", "load_gpen", "load_parsenet", "load_srmodel", "RetinaFace",
-           "load_retinaface", "ReconNetWrapper", "define_net_recon", "load_face3d_net"]
+           "load_retinaface", "ReconNetWrapper", "define_net_recon", "load_face3d_net", "FAN", "load_fan"]

@@ -188,6 +188,13 @@ def s3fd_state_dict(module):
     return sd
 
 
+# FAN-4 (59 pre-activation residual ConvBlocks, four stacks each adding bl + al onto ``previous``): the
+# heatmap magnitude grows stack by stack (gain 1.0: max |hm| 11, 123, 1.7e3, 1.2e4; gain 1.3: up to
+# 8.7e6).  Gain 0.8 keeps the last stack's max |hm| within [1, 1e3] (2.6, 11, 58, 227 on a 256x256
+# hash-noise crop; tests/golden/make_fan_golden.py asserts the range).
+FAN_SYNTH = dict(gain=0.8)
+
+
 # ----------------------------------------------------------------------------- inputs
 def hash_array(key: str, shape, lo: float = -1.0, hi: float = 1.0) -> np.ndarray:
     """Deterministic float32 array uniform in [lo, hi) (portable: no RNG state)."""
