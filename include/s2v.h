@@ -164,13 +164,27 @@ enum { S2V_PREC_F32 = 0, S2V_PREC_BF16X3 = 1, S2V_PREC_F16X3 = 2 };
  * ENet.py, DNet.py, base_blocks.py, ffc.py, transformer.py (inventory: SURVEY.md App. A). */
 int s2v_conv2d(const s2v_conv_params *p, s2v_stream_t stream);
 size_t s2v_conv2d_ws_bytes(const s2v_conv_params *p);
-/* The launch plan s2v_conv2d would use: out11 = {BM, BN, WAVES_M, AVEC, B_KN, splits, prec, NW, KS, PF,
- * PERSIST} of the conv_igemm<BM,BN,WAVES_M,AVEC,B_KN> (prec 0) or
- * conv_igemm_x3<BM,BN,WAVES_M,NW,KS,PF,AVEC,B_KN,prec-1> (prec 1 / 2) instance — conv_igemm_x3_persist<...>
- * with PERSIST (> 0) blocks under ``grid_cap``, conv_glds_x3<BM,BN,WAVES_M,KS,prec-1> when AVEC == 5 —
- * or {0, CO, TPP, LW, 0, 1, 0, ...} for conv_small_cpar<CO,TPP,LW> (conv_direct_small<CO> when TPP == 0),
- * or {0, cout, -QPT, PX, 0, 1, ...} for conv_smallk<QPT,PX>.  force_tile: 0 = planner, 1..6 (f32) / 1..12
- * (split precisions) a fixed tile of the selected precision's table (tests / tuning). */
+/* The launch plan s2v_conv2d would use, as eleven ints (host only, no device needed):
+ *   out11 = {BM, BN, WAVES_M, AVEC, CODE, splits, prec, NW, KS, PF, PERSIST}
+ * Tile kernels (BM > 0), told apart by AVEC and prec (out11[6]: 0 for the fp32 kernel, else the precision):
+ *   AVEC 0..3, prec 0   conv_igemm<BM,BN,WAVES_M,AVEC,B_KN>, CODE = B_KN.  AVEC is the A-operand mode: 0 direct
+ *                       32-channel slices, 1 generic float4 gather, 2 scalar gather, 3 reflect / nearest-x2 rows;
+ *   AVEC 0..4, prec > 0 conv_igemm_x3<BM,BN,WAVES_M,NW,KS,PF,AVEC,B_KN,prec-1> (4: buffer loads), CODE = B_KN;
+ *                       conv_igemm_x3_persist<...> with PERSIST (> 0) blocks under ``grid_cap``;
+ *   AVEC 5              conv_glds_x3<BM,BN,WAVES_M,KS,prec-1> (x_split inputs; NW 8, KS = LDS stages);
+ *   AVEC 6 / 7          conv_x3_nar<prec-1, AVEC-6> (BM 256, BN 64);
+ *   AVEC 8              conv_x3_halo<prec-1, BM/64, BN/64> (4 or 8 patch rows, 1 or 2 wave columns).
+ * Other kernels (BM == 0, BN = cout), told apart by CODE (slot 4) and the sign of slot 2:
+ *   {0, cout, TPP, LW, 0, 1}                 conv_small_cpar<cout,TPP,LW>; conv_direct_small<cout> when TPP == 0;
+ *   {0, cout, -QPT, 1, 0, 1}                 conv_smallk<QPT,1>;
+ *   {0, cout, -QPT, 1, 2000 + KT, 1}         conv_smallk4<QPT,KT> (KT 1 / 9 taps);
+ *   {0, cout, 0, 0, 1000 + KS, splits}       conv_halo_small<cout,KS> (KS 3 / 5 / 7);
+ *   {0, cout, NCS, 0, 3000 + KS, splits, prec}  conv_head_x3<prec-1,cout,KS,NCS> (KS 5 / 7);
+ *   {0, cout, 0, 0, 4000 + KT, 1}            conv_k4_mfma<KT> (KT 1 / 9 taps).
+ * force_tile: 0 = planner, else a fixed tile of the selected precision's table (tests / tuning): 1..6 for
+ * S2V_PREC_F32; 1..20 for the split precisions, where 1..15 are conv_igemm_x3 tiles (b_kn operands: the
+ * 4-wave ones), 16 / 17 conv_x3_nar and 18 / 19 / 20 conv_x3_halo (4 rows, 8 rows, 4 rows x 128 channels).
+ * A forced tile the launch cannot run is S2V_E_INVALID. */
 int s2v_conv2d_plan(const s2v_conv_params *p, int *out11);
 /* Up to S2V_CONV_GROUP_MAX independent convolutions as ONE kernel launch (a tile table over the members'
  * tile grids on one tile configuration, each member with its own split-K factor), plus one launch

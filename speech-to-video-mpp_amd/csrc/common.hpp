@@ -2,25 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
-#include "../../include/s2v.h"
+#include "host.hpp"
 
 namespace s2v {
-
-void set_error(const char *fmt, ...);
-int check_launch(const char *what);
-int device_cus();
-long long tune_get(int key);   // s2v_tune knobs (conv.hip)
-
-#define S2V_REQUIRE(cond, ...)            \
-    do {                                  \
-        if (!(cond)) {                    \
-            ::s2v::set_error(__VA_ARGS__);\
-            return S2V_E_INVALID;         \
-        }                                 \
-    } while (0)
 
 __device__ __forceinline__ float apply_act(float v, int act, float alpha) {
     switch (act) {
@@ -50,7 +34,5 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     i = i < 0 ? -i : i;
     return i >= n ? 2 * n - 2 - i : i;
 }
-
-inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace s2v

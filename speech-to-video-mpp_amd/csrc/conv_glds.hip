@@ -17,6 +17,8 @@
 // x3 kernels; only AMODE-0 convolutions (direct, zero padding, cin % 32 == 0, no prologue).
 #include "conv_x3_impl.hpp"
 
+#include "conv_launch.hpp"
+
 namespace s2v {
 
 __device__ __attribute__((aligned(256))) char g_zero_line[256];
@@ -229,7 +231,7 @@ __global__ __launch_bounds__(256) void split_act_kernel(const float *__restrict_
     }
 }
 
-// glds configurations (conv.hip kGlds): 0 = 256x256 (2 stages), 1 = 256x128 (3 stages),
+// glds configurations (conv_plan.cpp kGlds): 0 = 256x256 (2 stages), 1 = 256x128 (3 stages),
 // 2 = 512x128 (2 stages, 128x64 per wave).  Measured and dropped (r02, tools/glds_sweep.sh): s_setprio
 // for the younger half / around the MFMA clusters (+-1 %), 4-wave blocks with 128x128 wave tiles
 // (-11 % at 256x256, -11 % at 512x128).

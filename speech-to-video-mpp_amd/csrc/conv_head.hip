@@ -23,6 +23,8 @@
 // pre-scale (x_scale), the weight pre-scale (acc_scale) and the non-finite flag of the range guard.
 #include "conv_x3_impl.hpp"
 
+#include "conv_launch.hpp"
+
 namespace s2v {
 
 constexpr int kHeadM = 32;    // input columns of a strip (2 MFMA row blocks of 16)

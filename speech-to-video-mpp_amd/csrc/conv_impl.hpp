@@ -50,7 +50,7 @@ struct ConvArgs {
     float x_scale;          // split-precision A operand pre-scale (power of two; 1 = none)
     int *nonfinite;         // set to 1 when an accumulator is non-finite (or null)
     int vec4;               // the tile epilogues may write 4-channel quads (cout, ycs, y_bs multiples of 4, 16-byte
-                            // aligned y / scale / shift / res / nc_scale rows: conv.hip epi_vec4)
+                            // aligned y / scale / shift / res / nc_scale rows: conv_plan.cpp epi_vec4)
     int vgrid_x, vgrid_y, vgrid_z;   // x3 persistent launch: the tile grid gridDim.x blocks loop over
                                      // (s2v_conv_params.grid_cap); vgrid_x == 0: one block per tile
 };

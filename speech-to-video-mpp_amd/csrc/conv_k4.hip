@@ -14,6 +14,8 @@
 // in every precision mode (the products are fp32 MFMA: more precise than the split modes, the same as f32).
 #include "conv_impl.hpp"
 
+#include "conv_launch.hpp"
+
 namespace s2v {
 
 constexpr int kK4Tiles = 8;   // 32-pixel tiles per block

@@ -1,6 +1,8 @@
 // bf16 instances of the split-fp32 implicit-GEMM convolution (S2V_PREC_BF16X3; conv_x3_impl.hpp).
 #include "conv_x3_impl.hpp"
 
+#include "conv_launch.hpp"
+
 namespace s2v {
 extern template bool launch_conv_x3_part<0, 1>(int, const ConvArgs &, int, bool, dim3, hipStream_t);
 extern template bool launch_conv_x3_part<0, 2>(int, const ConvArgs &, int, bool, dim3, hipStream_t);

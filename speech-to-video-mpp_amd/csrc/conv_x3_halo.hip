@@ -13,12 +13,14 @@
 // of pre-split weights per tap still come from L2 (double-buffered LDS stages, one barrier per tap).
 // The next channel slice's halo is loaded into registers during the first taps.
 //
-// Conditions (conv.hip halo_ok): 3x3, stride 1, dilation 1, zero padding 1, direct input, cin % 32 == 0,
+// Conditions (conv_plan.cpp halo_ok): 3x3, stride 1, dilation 1, zero padding 1, direct input, cin % 32 == 0,
 // packed weights over whole 64-row slabs, 2^31-byte offsets, no pooled epilogue; ragged images run
 // partly empty last patches (the planner requires >= 85 % of the patch grid to be image).  Same products and the same per-slice MFMA order as conv_igemm_x3, but the K order is
 // channel-slice major over taps in the natural order (conv_x3_impl's kperm order is the same: tap
 // fastest), so results equal the LDS tiles bit for bit (tests/test_ops_gpu.py).
 #include "conv_x3_impl.hpp"
+
+#include "conv_launch.hpp"
 
 namespace s2v {
 

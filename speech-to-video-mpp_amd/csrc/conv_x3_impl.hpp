@@ -316,7 +316,7 @@ __device__ __forceinline__ void conv_x3_tile(const ConvArgs &a, int L, int gx, i
     const char *__restrict__ wtb = (const char *)wtf;                      // split view (packed)
     const int kt0 = split * a.tps;
     const int kt1 = min(a.ktiles, kt0 + a.tps);
-    // buffer loads: a partial last channel slice (1x1, cin % 8 == 0, conv.hip x3_partial_1x1)
+    // buffer loads: a partial last channel slice (1x1, cin % 8 == 0, conv_plan.cpp x3_partial_1x1)
     const int taps = a.kh * a.kw, nsl = BUF ? (a.cin + 31) >> 5 : a.cin >> 5;
     const bool kperm = (AMODE == 0 || AMODE == 3) && !BKN && taps > 1;
     const int ak = (tid & 7) * 4;
@@ -753,7 +753,7 @@ static bool launch_x3(const ConvArgs &a, int amode, bool bkn, dim3 grid, hipStre
     return true;
 }
 
-// x3 kernel configurations (index = the host planner's tile id, conv.hip kX3Tiles)
+// x3 kernel configurations (index = the host planner's tile id, conv_plan.cpp kX3Tiles)
 // the persistent form exists for the 256x256 tile with buffer-load A (the ENet style encoder's
 // layers; conv.hip only sets a.vgrid_* for that configuration)
 constexpr bool x3_has_persist(int cfg, int amode, bool bkn) { return cfg == 0 && amode == 4 && !bkn; }
@@ -810,9 +810,6 @@ int launch_conv_x3(int cfg, const ConvArgs &a, int amode, bool bkn, dim3 grid, h
     S2V_REQUIRE(ok, "conv2d: x3 configuration %d has no kernel for A mode %d%s", cfg, amode, bkn ? " (b_kn)" : "");
     return 0;
 }
-
-// grouped launches exist for the 4-wave 64x64 / 128x64 and the 8-wave 128x128 buffer-load tiles
-constexpr bool x3_has_group(int cfg) { return cfg == 1 || cfg == 3 || cfg == 4; }
 
 template <int ELT>
 int launch_conv_x3_group(int cfg, const ConvGroup &g, dim3 grid, hipStream_t s) {

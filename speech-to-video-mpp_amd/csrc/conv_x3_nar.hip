@@ -26,6 +26,8 @@
 // (the input loaded once per channel slice instead of once per tap).  Kept forced-only (force_tile 16 / 17).
 #include "conv_x3_impl.hpp"
 
+#include "conv_launch.hpp"
+
 namespace s2v {
 
 // NAR_ABL (timing ablation, never in the shipped build): 1 = every slice re-reads the first tap's A

@@ -113,7 +113,7 @@ _TLS = threading.local()
 
 def _grouping() -> bool:
     return getattr(_TLS, "grouping", False)
-# Tuned (x3 tile, split-K) of split-precision conv launches whose planner choice (csrc/conv.hip
+# Tuned (x3 tile, split-K) of split-precision conv launches whose planner choice (csrc/conv_plan.cpp
 # make_plan_x3's time model) measured slower than another configuration: a table measured on MI355X by
 # tools/tune_perfdb.py (every conv launch of the LNet / ENet / DNet forwards, each candidate tile and
 # split factor graph-timed against the planner's own choice), keyed by conv_key().  Only entries that

@@ -340,3 +340,34 @@ def test_planner_gives_narrow_3x3_layers_to_the_halo_kernel():
     assert rc == 0 and pl[3] == 8, pl
     rc, _ = _plan(4, 256, 256, 64, 64, stride=2, force_tile=18)
     assert rc != 0 and b"conv_x3_halo" in _lib.load().s2v_last_error()
+
+
+def test_planner_decisions_are_pinned():
+    """tests/golden/conv_plans.json pins what the conv planner (csrc/conv_plan.cpp) answers, on a 256-CU device or
+    none, for every conv / modconv / gemm / group launch of the engines of test_engine_dryrun.py at batch 1, 2 and 16
+    and for a synthetic sweep of the corners they do not reach, illegal launches with their messages included:
+    the return code, the eleven ints of s2v_conv2d_plan, s2v_conv2d_ws_bytes, s2v_conv2d_group_plan /
+    _group_ws_bytes and the s2v_last_error text, compared for equality.  The replay runs in a fresh process without
+    any S2V_* variable (the knobs are read once per process, and other tests change the tune values).
+
+    A deliberate planner change shows up as a diff of that file; regenerate it with
+
+        python tools/plan_table.py --record tests/golden/conv_plans.json
+    """
+    import sys
+    path = os.path.join(GOLDEN, "conv_plans.json")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("S2V_")}
+    run = subprocess.run([sys.executable, os.path.join(REPO, "tools", "plan_table.py"), "--replay", path], env=env,
+                         capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-2000:]
+    got = json.loads(run.stdout)
+    if got["cus"] not in (0, 256):
+        pytest.skip(f"recorded for 256 CUs (or no device), this device has {got['cus']}")
+    # the recorded counts: a regenerated fixture may grow, not lose launches unnoticed
+    assert len(got["engines"]) >= 885 and len(got["sweep"]) >= 1210 and len(got["groups"]) >= 25
+    for section in ("engines", "sweep", "groups"):
+        for r in got[section]:
+            assert r["got"] == r["want"], (section, r["p"])
+    routes = {r["route"] for s in ("engines", "sweep") for r in got[s]} - {None}
+    assert routes == {"glds", "head_x3", "halo_small", "small_cpar", "direct_small", "k4", "smallk", "smallk4", "x3_tile",
+                      "x3_nar", "x3_halo", "igemm"}, routes

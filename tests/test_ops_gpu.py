@@ -10,8 +10,10 @@ run in both arithmetic modes (``prec`` fixture):
   * f16x3  (the same split on v_mfma_f32_32x32x16_f16): 3e-6 * sum|a*b| — 3 * 2^-22 = 7.2e-7 per
            product in the f16 normal range (weights pre-scaled into it), plus the fp32 sums.
 """
+import contextlib
 import ctypes
 import math
+import re
 
 import numpy as np
 import pytest
@@ -152,6 +154,34 @@ CONV_CASES = [
     (1, 128, 9, 33, 2, 1, 1, 0, 1, "direct", "zero", 0, 0),
     (2, 32, 7, 11, 4, 1, 1, 0, 1, "direct", "zero", 0, 0),
     (1, 256, 5, 9, 1, 1, 1, 0, 1, "direct", "zero", 0, 0),
+    # one tiny shape per kernel family with the kernel the launch must run (a 14th element: per precision a
+    # regex of the symbol after "void s2v::", optionally the split-K factor / persistent blocks of the plan;
+    # "exact": the fp32 bound, for the fp32 VALU kernels; "cap": ops.x3_grid_cap)
+    (2, 32, 8, 8, 64, 3, 1, 1, 1, "direct", "zero", 0, 0,
+     {"f32": "conv_igemm<64, 64, 2, 0, 0>", "f16x3": "conv_igemm_x3<64, 64, 2, 4, 1, 1, 4, 0, 1>"}),
+    (2, 12, 8, 8, 64, 3, 1, 1, 1, "direct", "zero", 0, 0,
+     {"f32": "conv_igemm<64, 64, 2, 1, 0>", "f16x3": "conv_igemm_x3<.*, 1, 0, 1>"}),              # float4 gather
+    (2, 10, 8, 8, 64, 3, 1, 1, 1, "direct", "zero", 0, 0, {"f32": "conv_igemm<64, 64, 2, 2, 0>"}),    # scalar gather
+    (2, 32, 8, 8, 64, 3, 1, 1, 1, "direct", "reflect", 0, 0, {"f16x3": "conv_igemm_x3<.*, 3, 0, 1>"}),
+    (1, 256, 8, 8, 64, 3, 1, 1, 1, "direct", "zero", 0, 0, {"f16x3": ("conv_igemm_x3<.*>", 15)}),   # planner's split-K
+    (2, 32, 8, 8, 64, 3, 1, 1, 1, "direct", "zero", 16, 0, {"f16x3": "conv_x3_nar<1, 0>"}),
+    (2, 32, 8, 8, 64, 3, 1, 1, 1, "direct", "zero", 17, 0, {"f16x3": "conv_x3_nar<1, 1>"}),
+    (8, 32, 256, 64, 64, 3, 1, 1, 1, "direct", "zero", 0, 0, {"f16x3": "conv_x3_halo<1, 4, 1>"}),   # the planner's choice
+    (2, 32, 256, 64, 64, 3, 1, 1, 1, "direct", "zero", 0, 0, {"f16x3": "conv_igemm_x3<.*>"}),       # grid too small for it
+    (8, 32, 256, 64, 128, 3, 1, 1, 1, "direct", "zero", 0, 0, {"f16x3": "conv_x3_halo<1, 4, 2>"}),
+    (1, 32, 8, 64, 64, 3, 1, 1, 1, "direct", "zero", 19, 0, {"f16x3": "conv_x3_halo<1, 8, 1>"}),
+    (1, 64, 9, 30, 3, 7, 1, 3, 1, "direct", "zero", 0, 0, {"f32": ("conv_halo_small<3, 7>", 8), "exact": True}),
+    (1, 8, 9, 30, 3, 3, 1, 1, 1, "direct", "zero", 0, 0, {"f16x3": "conv_halo_small<3, 3>", "exact": True}),
+    (1, 128, 9, 10, 3, 1, 1, 0, 1, "direct", "zero", 0, 0, {"f16x3": "conv_small_cpar<3, 8, true>", "exact": True}),
+    (1, 32, 9, 10, 3, 1, 1, 0, 1, "direct", "zero", 0, 0, {"f16x3": "conv_small_cpar<3, 2, true>", "exact": True}),
+    (1, 2048, 9, 10, 3, 1, 1, 0, 1, "direct", "zero", 0, 0, {"f16x3": "conv_small_cpar<3, 8, false>", "exact": True}),
+    (1, 3, 9, 10, 1, 3, 1, 1, 1, "direct", "zero", 0, 0, {"f16x3": "conv_direct_small<1>", "exact": True}),
+    (1, 4, 9, 10, 16, 1, 1, 0, 1, "direct", "zero", 0, 0, {"f16x3": "conv_smallk4<1, 1>", "exact": True}),
+    (1, 4, 9, 10, 16, 3, 1, 1, 1, "direct", "zero", 0, 0, {"f32": "conv_smallk4<1, 9>", "exact": True}),
+    (1, 4, 9, 10, 512, 1, 1, 0, 1, "direct", "zero", 0, 0, {"f16x3": "conv_smallk4<2, 1>", "exact": True}),
+    (1, 8, 9, 10, 16, 1, 1, 0, 1, "direct", "zero", 0, 0, {"f16x3": "conv_smallk<1, 1>", "exact": True}),
+    (4, 64, 64, 64, 256, 3, 1, 1, 1, "direct", "zero", 1, 0,
+     {"f16x3": ("conv_igemm_x3_persist<256, 256, 2, 8, 1, 1, 4, 0, 1>", None, 8), "cap": 8}),
 ]
 
 
@@ -240,7 +270,8 @@ def halo_everywhere(ctx):
 
 @pytest.mark.parametrize("case", CONV_CASES, ids=[str(i) for i in range(len(CONV_CASES))])
 def test_conv2d(ctx, prec, case, request):
-    n, cin, h, w, cout, k, stride, pad, dil, mode, pad_mode, tile, splits = case
+    n, cin, h, w, cout, k, stride, pad, dil, mode, pad_mode, tile, splits = case[:13]
+    want = case[13] if len(case) > 13 else {}
     if cout <= 4 and w >= 96:
         request.getfixturevalue("halo_everywhere")
     if tile > 6 and prec == "f32":
@@ -286,10 +317,28 @@ def test_conv2d(ctx, prec, case, request):
             rv = nhwc(res.float())
             kwargs.update(act=ops.ACT_TANH, res=rv, res_after=True)
             exp = torch.tanh(exp) + res
-        ops.conv2d(ctx, nhwc(x.float()), cw, y, **kwargs)
+        plans = []
+
+        def hook(c, p, flops, launch):
+            plans.append(p.plan)
+            launch()
+        ops.CONV_HOOK = hook if want else None            # (the cases without a named kernel launch as before)
+        try:
+            with ops.x3_grid_cap(ctx, want["cap"]) if "cap" in want else contextlib.nullcontext():
+                ops.conv2d(ctx, nhwc(x.float()), cw, y, **kwargs)
+        finally:
+            ops.CONV_HOOK = None
+        # the kernel is asserted for variant 0 only: the nc_scale / residual epilogues of variants 1 and 2 rightly
+        # take some of these shapes to another kernel (conv_k4_mfma has a plain epilogue only)
+        if variant == 0 and prec in want:
+            pat, *rest = want[prec] if isinstance(want[prec], tuple) else (want[prec],)
+            sym = ops.plan_symbol(plans[0])
+            assert len(plans) == 1 and re.fullmatch(r"void s2v::" + pat + r"\(.*\)", sym), sym
+            assert not rest or rest[0] is None or plans[0][5] == rest[0], plans[0]   # split-K factor
+            assert len(rest) < 2 or plans[0][10] == rest[1], plans[0]            # persistent blocks
         got = to_nchw(y)
         err = (got - exp).abs()
-        lim = REL[prec] * (bound + 1) + 1e-6
+        lim = (REL["f32"] if want.get("exact") and prec in want else REL[prec]) * (bound + 1) + 1e-6
         if variant == 1:
             lim = lim * 1.5
         assert (err <= lim).all(), f"variant {variant}: max err {err.max():.3e}, rel {(err / lim).max():.2f}"
@@ -715,7 +764,9 @@ def test_small_cout_conv(ctx, prec, cin, k, cout):
     (2, 32, 9, 61, 7, 1, "reflect", ops.ACT_NONE),
     (2, 256, 20, 64, 7, 2, "zero", ops.ACT_NONE),          # DNet flow head form: 4 channel groups, split-K fold
     (1, 128, 9, 70, 5, 3, "reflect", ops.ACT_TANH),
-    (2, 64, 5, 40, 7, 3, "reflect", ops.ACT_NONE)])        # 5 rows (odd band): the 2-row loop's unread extra
+    (2, 64, 5, 40, 7, 3, "reflect", ops.ACT_NONE),         # 5 rows (odd band): the 2-row loop's unread extra
+    (1, 32, 9, 30, 7, 3, "zero", ops.ACT_NONE),            # one 32-channel slice, 7x7
+    (1, 128, 9, 30, 5, 2, "zero", ops.ACT_NONE)])          # two channel groups (split-K fold), 5x5
 def test_conv_head_x3(ctx, prec, n, cin, h, w, k, cout, pad_mode, act):
     """Cout <= 4 wide-filter heads (conv_head.hip: kx in N, ky in K, an LDS ring of split input rows)
     in the split precisions; exact fp32 VALU (conv_halo_small / conv_small_cpar) in f32.  Against the
@@ -1161,7 +1212,8 @@ def test_conv2d_post_and_dup_epilogue(ctx, prec, tile, splits, nc):
 
 @pytest.mark.parametrize("n,h,w,cout,k,noise", [(3, 7, 9, 32, 3, False), (2, 16, 16, 96, 3, True),
                                                  (2, 20, 24, 256, 3, True), (3, 11, 13, 64, 1, False),
-                                                 (1, 33, 40, 256, 1, True)])
+                                                 (1, 33, 40, 256, 1, True), (1, 9, 10, 32, 3, False),
+                                                 (1, 9, 10, 64, 1, False)])
 def test_conv_k4_exact_fp32(ctx, prec, n, h, w, cout, k, noise):
     """4-channel "same" convs run on conv_k4_mfma (csrc/conv_k4.hip) in every precision mode, in exact fp32 (MFMA
     v_mfma_f32_32x32x2f32): against fp64 at the fp32 bound, including partial last tiles (h*w not a multiple of 32),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time every split-precision tile (force_tile 1..8) of the implicit-GEMM conv on the model's
-representative shapes (HIP events, f16x3 by default) — the data behind conv.hip's kX3Tiles rates.
+representative shapes (HIP events, f16x3 by default) — the data behind conv_plan.cpp's kX3Tiles rates.
 
     python tools/tile_sweep.py [--prec f16x3] [--iters 10]
 """
