@@ -651,6 +651,33 @@ int s2v_restore_paste(const unsigned char *face, int S, const double *M, const f
  * (align_img + np.array(im) / 255. + torch.tensor) for every frame of the clip at once. */
 int s2v_pil_resize_crop(const unsigned char *x, int n, int h0, int w0, long long xis, const int *params, int filter,
                         float *y, int oh, int ow, int ycs, s2v_stream_t stream);
+
+/* ---- STIT reference stitch (inference.py:341-367 datagen; futils/alignment_stit.py) -------------- */
+
+/* Pillow's Image.transform((ow, oh), QUAD, data, BILINEAR) (libImaging/Geometry.c) for n uint8 HWC frames
+ * of c = 3 or 4 independent bands (Pillow's RGB / RGBX; not the premultiplied RGBA path) in one launch:
+ * element (b, y, x, ch) at x + b*xis + y*xrs + x*c + ch (strides in bytes), output likewise with c channels.
+ * The output must not overlap the frames.  table: DEVICE double [n][12] = (a0..a7, left, top, width, height):
+ * the eight coefficients as Image.__transformer forms them from (nw, sw, se, ne) and the output
+ * size, relative to the source sub-rectangle (crop_image's crop box, alignment_stit.py:84-92) that the
+ * last four give; the box is clamped into the frame.  Per output pixel xin = a0 + a1 x' + a2 y' + a3 x' y'
+ * at x' = x + 0.5 (yin with a4..a7), fp64 without FMA; outside [0, width) x [0, height) the pixel is 0,
+ * otherwise bilinear at (xin - 0.5, yin - 0.5) with clamped neighbours and (UINT8) truncation. */
+int s2v_pil_transform_quad(const unsigned char *x, int n, int h, int w, int c, long long xrs, long long xis,
+                           const double *table, unsigned char *y, int oh, int ow, long long yrs, long long yis,
+                           s2v_stream_t stream);
+/* paste_image (alignment_stit.py:14-18) in one pass for n frames: the crop [sh][sw][cc] (cc 3: alpha 255;
+ * cc 4: RGBA, through Pillow's premultiplied RGBa round trip) under Image.transform(PERSPECTIVE, BILINEAR)
+ * with coeffs (DEVICE double [n][8]: xin = (a0 x' + a1 y' + a2) / (a6 x' + a7 y' + 1), yin with a3..a5),
+ * then paste(projected, mask=projected) over the target [h][w][tc] (a 4th target channel is ignored):
+ * out = DIV255(target * (255 - alpha) + projected * alpha) per band.  Output RGB with yc = 3 channels, or 4
+ * with alpha 255.  target == y (same layout) pastes in place; any other overlap of y with the target, and any
+ * overlap of y with the crop, is rejected. */
+int s2v_pil_perspective_paste(const unsigned char *crop, int n, int sh, int sw, int cc, long long crs,
+                              long long cis, const double *coeffs, const unsigned char *target, int h, int w,
+                              int tc, long long trs, long long tis, unsigned char *y, int yc, long long yrs,
+                              long long yis, s2v_stream_t stream);
+
 /* nn.AdaptiveAvgPool2d((1, 1)) on NHWC fp32: y[b][c] = mean of x[b][0..hw)[c] (fp64 sum)
  * (face3d models/networks.py ResNet._forward_impl avgpool). */
 int s2v_spatial_mean_nhwc(const float *x, int n, int hw, int c, float *y, s2v_stream_t stream);

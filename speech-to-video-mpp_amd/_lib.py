@@ -175,6 +175,10 @@ _SIGS = {
                                                                              _c_int, _vp]),
     "s2v_pil_resize_crop": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_ll, _vp, _c_int, _vp, _c_int, _c_int, _c_int,
                                      _vp]),
+    "s2v_pil_transform_quad": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _vp, _vp, _c_int, _c_int,
+                                        _c_ll, _c_ll, _vp]),
+    "s2v_pil_perspective_paste": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _vp, _vp, _c_int,
+                                           _c_int, _c_int, _c_ll, _c_ll, _vp, _c_int, _c_ll, _c_ll, _vp]),
     "s2v_spatial_mean_nhwc": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp]),
     "s2v_last_error": (ctypes.c_char_p, []),
     "s2v_device_cus": (_c_int, []),

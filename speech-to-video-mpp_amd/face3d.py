@@ -181,6 +181,11 @@ class KeypointExtractor:
                     out.append(np.asarray(lms[0]))
         return out
 
+    def first_faces(self, images):
+        """Per frame the first face's [68, 2] points, or all -1 without a face, with no reuse of earlier points:
+        for callers that carry the reuse rule across calls themselves (stitch.Stitcher).  Counts ``misses``."""
+        return self._first_faces(images)
+
     def extract_keypoint(self, images, name=None, info=True):
         """A list of frames (or one [N,H,W,3] array / device tensor) -> keypoints [N, 68, 2]; one frame
         [H,W,3] -> [68, 2].  ``name``: also written with np.savetxt to <name without extension>.txt."""

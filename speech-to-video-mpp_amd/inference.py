@@ -29,6 +29,11 @@ Steps (reference file:line in brackets):
     FaceEnhancement(in_size 512, use_sr False) on every stabilised reference before ENet
     [inference.py:224-238] (needs real RetinaFace / ParseNet weights: synthetic ones detect no face,
     and the reference raises on a frame without one);
+  * --stitch: datagen's reference construction [inference.py:348-367; futils/alignment_stit.py] on every
+    stabilised reference before ENet (s2v_amd.stitch.Stitcher): the 68 FAN landmarks of the stabilised frame ->
+    the rotated square around eyes and mouth -> Pillow QUAD crop -> inverse perspective paste over the original
+    crop, then the two cv2 resizes into the face box and back.  Synthetic FAN weights give points that are no
+    face: a frame whose quad is not finite or needs the reference's shrink branch raises, as the reference does;
   * each 384x384 prediction resized into the box and pasted into its frame [inference.py:287-291];
   * --enhance: FaceEnhancement (SR x2, RetinaFace, GPEN-2048, parse-mask paste) on each pasted frame
     against the 2x frame [inference.py:228-231, :317-328]; needs real checkpoints (synthetic
@@ -251,23 +256,57 @@ def _landmarks(frames_bgr: torch.Tensor, ckpt_dir, dev, detector=None):
     """facing.py:89-97: KeypointExtractor().extract_keypoint on the RGB frames -> (landmarks [n, 68, 2],
     FAN weight kind, frames without a face).  FAN weights from <checkpoints>/2DFAN4.pth, or the synthetic
     FAN_SYNTH preset without it; the boxes come from the S3FD detector of _face_detector."""
-    from . import face3d, models, synth
-    from .models.fan_arch import FANParams
+    from . import face3d
     if detector is None:
-        path = os.path.join(ckpt_dir or "", "2DFAN4.pth")
-        if ckpt_dir and os.path.exists(path):
-            fan, kind = models.load_fan(path), "2DFAN4 checkpoint"
-        else:
-            fan = models.FAN()
-            fan.load_state_dict(synth.synth_torch_state_dict(FANParams(), **synth.FAN_SYNTH), strict=True)
-            fan, kind = fan.eval(), "2DFAN4 synthetic"
-        detector, _ = _face_detector(ckpt_dir, dev)
-        detector.face_alignment_net = fan
+        detector, kind = _landmark_detector(ckpt_dir, dev)
     else:
         kind = "given detector"
     kp = face3d.KeypointExtractor(detector)
     lms = kp.extract_keypoint(frames_bgr[..., [2, 1, 0]].contiguous(), info=False)
     return lms.astype(np.float32), kind, kp.misses
+
+
+def _landmark_detector(ckpt_dir, dev):
+    """KeypointExtractor's detector: FaceAlignment over S3FD (_face_detector) with the FAN weights of
+    <checkpoints>/2DFAN4.pth, or the synthetic FAN_SYNTH preset without it -> (detector, FAN weight kind)."""
+    from . import models, synth
+    from .models.fan_arch import FANParams
+    path = os.path.join(ckpt_dir or "", "2DFAN4.pth")
+    if ckpt_dir and os.path.exists(path):
+        fan, kind = models.load_fan(path), "2DFAN4 checkpoint"
+    else:
+        fan = models.FAN()
+        fan.load_state_dict(synth.synth_torch_state_dict(FANParams(), **synth.FAN_SYNTH), strict=True)
+        fan, kind = fan.eval(), "2DFAN4 synthetic"
+    detector, _ = _face_detector(ckpt_dir, dev)
+    detector.face_alignment_net = fan
+    return detector, kind
+
+
+class BoxedStitch:
+    """datagen's references for ``run`` (inference.py:359-367): stitch.Stitcher on each batch, then the pasted
+    256 x 256 image resized into the frame's face box and the reference cut there again (:364-367).  In ``run``
+    the paste box and the face_detect box are one box, so that is cv2.resize to the box size and back: the
+    references carry the same two resamplings.  ``boxes``: (y1, y2, x1, x2) per frame of the clip, taken in
+    call order."""
+
+    def __init__(self, stitcher, boxes):
+        self.stitcher, self.boxes, self.k = stitcher, list(boxes), 0
+
+    @property
+    def misses(self):
+        return self.stitcher.misses
+
+    def __call__(self, ref_u8, base_u8):
+        from . import post
+        out = self.stitcher(ref_u8, base_u8).permute(0, 2, 3, 1).contiguous()
+        h, w = out.shape[1:3]
+        for i in range(out.shape[0]):
+            y1, y2, x1, x2 = self.boxes[self.k]
+            self.k += 1
+            boxed = post.resize_linear(out[i], (x2 - x1, y2 - y1))
+            post.resize_linear(boxed, (w, h), out=out[i])
+        return out.permute(0, 3, 1, 2).contiguous()
 
 
 def _face_detector(ckpt_dir, dev):
@@ -313,7 +352,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         ckpt_dir: str | None = None, enhance: bool = False, device: str = "cuda", ref_enhance: bool = False,
         ref_hook=None, restore: bool = True, restorer=None, enhancer=None, face_det: bool = False,
         pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None,
-        landmarks: bool = False, landmark_detector=None):
+        landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -328,7 +367,11 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     ``landmarks``: the frames' 68 FAN landmarks (_landmarks; ``landmark_detector``: an object with
     get_landmarks_from_batch) drive the 3DMM extraction instead of the no-landmark path; ``meta`` gains
     ``landmarks`` (the FAN weight kind), ``landmark_misses`` (frames without a face) and ``landmark_rejects``
-    (_usable_landmarks), the result gains ``semantic`` [n, 262]."""
+    (_usable_landmarks), the result gains ``semantic`` [n, 262].  ``stitch``: datagen's reference stitch
+    (stitch.Stitcher through BoxedStitch) on the stabilised references, over ``stitch_detector`` (an object with
+    get_landmarks_from_batch; else S3FD + FAN from ``ckpt_dir`` or the synthetic presets, whose points are no
+    face: a frame with an unusable quad raises ValueError); ``meta`` gains ``stitch``, ``stitch_misses`` (frames
+    without a face, which reuse their predecessor's points) and ``stitch_landmarks`` (the FAN weight kind)."""
     from . import audio, pipeline, post, synth
     dev = torch.device(device)
     t0 = time.time()
@@ -372,7 +415,17 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     coeffs = torch.from_numpy(pipeline.dnet_coefficients(semantic, expression, False, 0, n)).to(dev)
     if ref_enhance and ref_hook is None:
         ref_hook = _ref_enhancer(ckpt_dir, dev)
-    pipe = pipeline.LipSyncPipeline(dnet, enet, device=dev, batch=batch, graph=False, ref_hook=ref_hook)
+    stitcher = None
+    if stitch:
+        from . import face3d
+        from . import stitch as stitching
+        if stitch_detector is None:
+            stitch_detector, stkind = _landmark_detector(ckpt_dir, dev)
+        else:
+            stkind = "given detector"
+        stitcher = BoxedStitch(stitching.Stitcher(face3d.KeypointExtractor(stitch_detector), image_size=256), boxes)
+    pipe = pipeline.LipSyncPipeline(dnet, enet, device=dev, batch=batch, graph=False, ref_hook=ref_hook,
+                                    stitch=stitcher)
     preds = pipe.run(chunks[:n], src, coeffs)                                       # [n,3,384,384] uint8
     out = frames.clone()
     hwc = preds.permute(0, 2, 3, 1).contiguous()
@@ -409,6 +462,10 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     if face_det:
         meta["boxes"] = [list(b) for b in boxes]
         meta["box_source"] = box_source
+    if stitch:
+        meta["stitch"] = True
+        meta["stitch_misses"] = int(stitcher.misses)
+        meta["stitch_landmarks"] = stkind
     res = {"frames": out, "preds": preds, "enhanced": enhanced, "meta": meta}
     if landmarks:
         meta["landmarks"] = lkind
@@ -437,6 +494,10 @@ def build_parser():
     ap.add_argument("--face_det_batch_size", type=int, default=4, help="with --face_det: frames per detector batch")
     ap.add_argument("--landmarks", action="store_true",
                     help="68 FAN landmarks per frame (S3FD + 2DFAN4) drive the 3DMM extraction")
+    ap.add_argument("--stitch", action="store_true",
+                    help="datagen's reference stitch: quad crop of each stabilised reference pasted over the original "
+                         "crop (needs real S3FD / FAN weights: synthetic ones give points that are no face, and a "
+                         "frame with an unusable quad raises)")
     return ap
 
 
@@ -446,7 +507,8 @@ def main(argv=None):
         raise SystemExit("--pads takes four integers: top bottom left right")
     r = run(a.face, a.audio, a.max_frames, a.LNet_batch_size, a.box_frac, a.checkpoints, a.enhance,
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
-            nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks)
+            nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
+            stitch=a.stitch)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     arrays = {"frames": r["frames"].cpu().numpy(), "preds": r["preds"].cpu().numpy()}
     if r["enhanced"] is not None:

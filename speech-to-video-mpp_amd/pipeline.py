@@ -79,7 +79,7 @@ class LipSyncPipeline:
     side streams and noise counters (the models' per-lane ops.Ctx) and its own graph buffers."""
 
     def __init__(self, dnet, enet, device="cuda", batch: int = 16, graph: bool = True, lanes: int = 1,
-                 ref_hook=None):
+                 ref_hook=None, stitch=None):
         self.dnet, self.enet = dnet, enet
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -91,6 +91,9 @@ class LipSyncPipeline:
         self.graph = graph          # full batches of ``run`` replay captured HIP graphs
         self.lanes = lanes
         self.ref_hook = ref_hook    # Step 5 (inference.py:234-238) on the uint8 references; eager batches only
+        # datagen's reference stitch (inference.py:348-364; stitch.Stitcher, or any callable on (uint8 references
+        # [b,3,h,w], uint8 original crops [b,h,w,3])); its landmarks go through the host: eager batches only
+        self.stitch = stitch
         self._runner = None
         self.reruns = 0             # replayed batches run again in bf16x3 after an f16x3 range overflow
 
@@ -107,6 +110,11 @@ class LipSyncPipeline:
         ops.S2V.lipsync_inputs_(src.contiguous(), fake, ref_u8, face6, gt)
         if self.ref_hook is not None:                 # the enhanced references replace ref / 255 (datagen)
             ref_u8 = self.ref_hook(ref_u8).contiguous()
+        if self.stitch is not None:                   # quad crop of the reference pasted over the original crop
+            base = torch.empty((b, 3, h, w), dtype=torch.uint8, device=self.device)
+            ops.S2V.to_u8_(src.contiguous(), base, -1.0, 1.0, 127.5, 1.0)       # the uint8 pixels face6 is built from
+            ref_u8 = self.stitch(ref_u8, base.permute(0, 2, 3, 1).contiguous()).contiguous()
+        if self.ref_hook is not None or self.stitch is not None:
             ops.S2V.lipsync_inputs_(src.contiguous(), None, ref_u8, face6, gt)
         pred, _ = self.enet(mel, face6, gt, lane=lane)
         ops.S2V.to_u8_(pred, out_u8, 0.0, 1.0, 255.0, 0.0)             # inference.py:267, :288
@@ -130,7 +138,7 @@ class LipSyncPipeline:
         for k, b0 in enumerate(range(0, n, self.batch)):
             b1 = min(n, b0 + self.batch)
             m, s, c = mel_chunks[start + b0: start + b1], src[b0:b1], coeffs[b0:b1]
-            if self.graph and b1 - b0 == self.batch and self.ref_hook is None:
+            if self.graph and b1 - b0 == self.batch and self.ref_hook is None and self.stitch is None:
                 runner = self._graph_runner(m, s, c)
                 dst = out[b0:b1]
                 lane = runner.next_lane()
