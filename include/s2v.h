@@ -713,6 +713,29 @@ int s2v_fan_crop(const unsigned char *frames, int n, int h, int w, const int *ta
 int s2v_fan_peaks(const float *hm, int n, int h, int w, int c, long long cs, float *preds, float *vals,
                   s2v_stream_t stream);
 
+/* ---- GANimation upper-face editing (third_part/ganimation_replicate; inference.py:269-288) ---- */
+
+/* The SplitGenerator input (model_utils.py:474-478) of n uint8 HWC originals [h][w][3] (element (b, y, x, ch)
+ * at x + b*xis + y*xrs + x*3 + ch, pitches in bytes): y fp32 NHWC [n][oh][ow][20], 16-byte aligned, channels
+ * 0-2 = F.interpolate(u8 / 255 * 2 - 1, (oh, ow), 'bilinear', align_corners=False) (the division in fp32),
+ * channels 3-19 = aus[b][0..17) (device fp32 [n][17]). */
+int s2v_gani_input(const unsigned char *x, int n, int h, int w, long long xrs, long long xis, const float *aus,
+                   float *y, int oh, int ow, s2v_stream_t stream);
+/* The generator's tops and GANimationModel.forward (ganimation.py:52-53) on the raw output of the stacked
+ * head conv: head NHWC [n][h][w] with pixel pitch head_cs (channels 0-2 colour logits, 3 the mask logit), in
+ * the generator input (pixel pitch in_cs, channels 0-2 the source image); pitches multiples of 4, both
+ * 16-byte aligned.  Outputs NCHW: color_mask [n][3][h][w] = tanh, aus_mask [n][1][h][w] = a = sigmoid,
+ * fake_img [n][3][h][w] = a * src + (1 - a) * color. */
+int s2v_gani_blend(const float *head, long long head_cs, const float *in, long long in_cs, int n, int h, int w,
+                   float *color_mask, float *aus_mask, float *fake_img, s2v_stream_t stream);
+/* inference.py:274-288 on pred fp32 NCHW [n][3][ph][pw] (unclamped) and the uint8 HWC originals [ph][pw][3]
+ * (pitches ors / ois in bytes): cur = F.interpolate(fake / 2 + 0.5, (ph, pw), 'bilinear') of fake fp32 NCHW
+ * [n][3][fh][fw], or orig / 255 when fake is NULL (up_face 'original'); mask = (row >= ph / 2 or orig == 0) per
+ * element; v = clamp(pred, 0, 1) * mask + cur * (1 - mask).  y NCHW [n][3][ph][pw]: fp32 v (out_u8 0) or
+ * uint8(v * 255) truncated (out_u8 1). */
+int s2v_gani_compose(const float *pred, const unsigned char *orig, long long ors, long long ois, const float *fake,
+                     int fh, int fw, int n, int ph, int pw, void *y, int out_u8, s2v_stream_t stream);
+
 const char *s2v_last_error(void);
 /* number of compute units of the current device (0 if no device) */
 int s2v_device_cus(void);

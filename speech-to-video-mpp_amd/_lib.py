@@ -180,6 +180,10 @@ _SIGS = {
     "s2v_pil_perspective_paste": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _vp, _vp, _c_int,
                                            _c_int, _c_int, _c_ll, _c_ll, _vp, _c_int, _c_ll, _c_ll, _vp]),
     "s2v_spatial_mean_nhwc": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp]),
+    "s2v_gani_input": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_ll, _c_ll, _vp, _vp, _c_int, _c_int, _vp]),
+    "s2v_gani_blend": (_c_int, [_vp, _c_ll, _vp, _c_ll, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "s2v_gani_compose": (_c_int, [_vp, _vp, _c_ll, _c_ll, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int,
+                                  _vp]),
     "s2v_last_error": (ctypes.c_char_p, []),
     "s2v_device_cus": (_c_int, []),
     "s2v_version": (ctypes.c_char_p, []),

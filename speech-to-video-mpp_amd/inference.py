@@ -34,6 +34,12 @@ Steps (reference file:line in brackets):
     the rotated square around eyes and mouth -> Pillow QUAD crop -> inverse perspective paste over the original
     crop, then the two cv2 resizes into the face box and back.  Synthetic FAN weights give points that are no
     face: a frame whose quad is not finite or needs the reference's shrink branch raises, as the reference does;
+  * --up_face sad|angry|surprise with --without_rl1: GANimation's upper-face edit [inference.py:250-253, :269-286]
+    (s2v_amd.ganimation): the 384x384 original crops, resized to 128x128, go through SplitGenerator with the
+    expression's action units; the edited faces, resized back, replace the prediction wherever the network's
+    masked input was not zero (the upper half).  --without_rl1 alone composites the unedited crops.  Weights from
+    <checkpoints>/30_net_gen.pth, or the synthetic preset without it.  --up_face without --without_rl1 changes
+    nothing (the reference computes the edit and drops it; here it is not computed);
   * each 384x384 prediction resized into the box and pasted into its frame [inference.py:287-291];
   * --enhance: FaceEnhancement (SR x2, RetinaFace, GPEN-2048, parse-mask paste) on each pasted frame
     against the 2x frame [inference.py:228-231, :317-328]; needs real checkpoints (synthetic
@@ -326,6 +332,20 @@ def _face_detector(ckpt_dir, dev):
                                         detector=sfd), kind
 
 
+def _up_face_model(ckpt_dir, dev):
+    """inference.py:250-253: GANimationModel().initialize() / setup() with the generator of
+    <checkpoints>/30_net_gen.pth, or the synthetic GANIMATION_SYNTH preset without it -> (model, weight kind)."""
+    from . import ganimation, models, synth
+    path = os.path.join(ckpt_dir or "", ganimation.CKPT_NAME)
+    if ckpt_dir and os.path.exists(path):
+        net, kind = models.load_ganimation(path), "30_net_gen checkpoint"
+    else:
+        net = models.SplitGenerator()
+        net.load_state_dict(synth.synth_torch_state_dict(net, **synth.GANIMATION_SYNTH), strict=True)
+        net, kind = net.eval(), "30_net_gen synthetic"
+    return ganimation.GANimationModel().initialize(net_gen=net, device=dev).setup(), kind
+
+
 def _ref_enhancer(ckpt_dir, dev):
     """inference.py:224-226: FaceEnhancement(in_size=512, channel_multiplier=2, narrow=1, sr_scale=4,
     model='GPEN-BFR-512', use_sr=False) as a hook on the stabilised uint8 RGB references."""
@@ -352,7 +372,8 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         ckpt_dir: str | None = None, enhance: bool = False, device: str = "cuda", ref_enhance: bool = False,
         ref_hook=None, restore: bool = True, restorer=None, enhancer=None, face_det: bool = False,
         pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None,
-        landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None):
+        landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None,
+        up_face: str = "original", without_rl1: bool = False, up_face_model=None):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -371,8 +392,15 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     (stitch.Stitcher through BoxedStitch) on the stabilised references, over ``stitch_detector`` (an object with
     get_landmarks_from_batch; else S3FD + FAN from ``ckpt_dir`` or the synthetic presets, whose points are no
     face: a frame with an unusable quad raises ValueError); ``meta`` gains ``stitch``, ``stitch_misses`` (frames
-    without a face, which reuse their predecessor's points) and ``stitch_landmarks`` (the FAN weight kind)."""
+    without a face, which reuse their predecessor's points) and ``stitch_landmarks`` (the FAN weight kind).
+    ``up_face`` ('original', 'sad', 'angry', 'surprise') / ``without_rl1``: GANimation's upper-face edit and the
+    composite of inference.py:269-286 (``up_face_model``: an initialised ganimation.GANimationModel, else one
+    over ``ckpt_dir``/30_net_gen.pth or the synthetic preset); ``meta`` gains ``up_face``, ``without_rl1`` and
+    ``up_face_weights``."""
     from . import audio, pipeline, post, synth
+    if up_face != "original":
+        from . import ganimation
+        ganimation.check_up_face(up_face)                  # ValueError before anything runs
     dev = torch.device(device)
     t0 = time.time()
     frames_np, fps, src_kind = _frames(face, max_frames)
@@ -424,9 +452,23 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         else:
             stkind = "given detector"
         stitcher = BoxedStitch(stitching.Stitcher(face3d.KeypointExtractor(stitch_detector), image_size=256), boxes)
+    ukind = None
+    if up_face != "original" and up_face_model is None:
+        up_face_model, ukind = _up_face_model(ckpt_dir, dev)                        # inference.py:250-253
+    elif up_face != "original":
+        ukind = "given model"
+    orig = None
+    if without_rl1:
+        # img_original (inference.py:384, :396): cv2.resize(oface, (img_size, img_size)), in the predictions' RGB
+        orig = torch.empty((n, 384, 384, 3), dtype=torch.uint8, device=dev)
+        for i, (by1, by2, bx1, bx2) in enumerate(boxes):
+            post.resize_linear(frames[i, by1:by2, bx1:bx2], (384, 384), out=orig[i])
+        orig = orig[..., [2, 1, 0]].contiguous()
     pipe = pipeline.LipSyncPipeline(dnet, enet, device=dev, batch=batch, graph=False, ref_hook=ref_hook,
-                                    stitch=stitcher)
-    preds = pipe.run(chunks[:n], src, coeffs)                                       # [n,3,384,384] uint8
+                                    stitch=stitcher, up_face=up_face_model if up_face != "original" else None,
+                                    up_face_name=up_face if up_face != "original" else None,
+                                    without_rl1=without_rl1)
+    preds = pipe.run(chunks[:n], src, coeffs, orig_u8=orig)                         # [n,3,384,384] uint8
     out = frames.clone()
     hwc = preds.permute(0, 2, 3, 1).contiguous()
     for i, (by1, by2, bx1, bx2) in enumerate(boxes):                                # inference.py:287-291
@@ -457,7 +499,8 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     meta = {"frames": n, "frame_hw": [int(H), int(W)], "fps": fps, "video": src_kind, "weights": wkind,
             "mel_cols": int(mel.shape[1]), "mel_windows": int(chunks.shape[0]), "wav_samples_16k": int(len(wav)),
             "box": [y1, y2, x1, x2], "semantic": skind, "ref_enhance": ref_hook is not None,
-            "restore": bool(enhance and restore),
+            "restore": bool(enhance and restore), "up_face": up_face, "without_rl1": bool(without_rl1),
+            "up_face_weights": ukind,
             "seconds": round(time.time() - t0, 3)}
     if face_det:
         meta["boxes"] = [list(b) for b in boxes]
@@ -498,6 +541,12 @@ def build_parser():
                     help="datagen's reference stitch: quad crop of each stabilised reference pasted over the original "
                          "crop (needs real S3FD / FAN weights: synthetic ones give points that are no face, and a "
                          "frame with an unusable quad raises)")
+    ap.add_argument("--up_face", default="original",
+                    help="upper-face expression edit by GANimation: original (none), sad, angry or surprise; it "
+                         "reaches the frames only with --without_rl1")
+    ap.add_argument("--without_rl1", default=False, action="store_true",
+                    help="composite the (edited) original crop over the prediction wherever the masked input was "
+                         "not zero: the upper half of the face")
     return ap
 
 
@@ -508,7 +557,7 @@ def main(argv=None):
     r = run(a.face, a.audio, a.max_frames, a.LNet_batch_size, a.box_frac, a.checkpoints, a.enhance,
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
             nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
-            stitch=a.stitch)
+            stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     arrays = {"frames": r["frames"].cpu().numpy(), "preds": r["preds"].cpu().numpy()}
     if r["enhanced"] is not None:

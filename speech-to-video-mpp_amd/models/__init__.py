@@ -16,7 +16,8 @@ import torch
 
 from .. import ops
 from ..ops import NHWC
-from . import arch, enhancer_arch, face3d_arch, fan_arch, parse_arch, retinaface_arch, s3fd_arch, sr_arch
+from . import (arch, enhancer_arch, face3d_arch, fan_arch, ganimation_arch, parse_arch, retinaface_arch, s3fd_arch,
+               sr_arch)
 
 
 def _fold5(x, dim):
@@ -379,6 +380,51 @@ class FAN(_EngineMixin, fan_arch.FANParams):
         return eng.to_nchw(self._guarded(ctx, lambda: eng.forward(ctx, x4)))
 
 
+class SplitGenerator(_EngineMixin, ganimation_arch.SplitGeneratorParams):
+    """third_part/ganimation_replicate/model/model_utils.py:419-482 as GANimationModel.initialize builds it
+    (define_splitG(3, 17, 64, norm='instance'): six ResnetBlocks, zero padding)."""
+
+    def _build_engine(self, sd, device):
+        from ..engine.ganimation import GANimationEngine
+        return GANimationEngine(sd, device)
+
+    def forward_nhwc(self, x20: NHWC, lane: int = 0):
+        """x20: NHWC [B,H,W,20] fp32 (image in [-1, 1] | the 17 action units as constant channels; H, W
+        multiples of 4) -> (raw head logits NHWC [B,H,W,4]: colour 0-2, mask 3; embed NHWC [B,H,W,64]) and the
+        lane context they were computed on."""
+        ganimation_arch.check_input(x20.h, x20.w)
+        eng, ctx = self._engine(x20.t.device, lane)
+        return self._guarded(ctx, lambda: eng.forward(ctx, x20)), ctx
+
+    @staticmethod
+    def blend(ctx, head: NHWC, x20: NHWC):
+        """s2v_gani_blend: (color_mask [B,3,H,W], aus_mask [B,1,H,W], fake_img [B,3,H,W]) from the raw head
+        logits and the generator input."""
+        n, h, w, dev = head.n, head.h, head.w, head.t.device
+        color, mask, fake = (ops.empty((n, c, h, w), dev) for c in (3, 1, 3))
+        ops.check(ctx.lib.s2v_gani_blend(head.ptr, head.cs, x20.ptr, x20.cs, n, h, w, color.data_ptr(),
+                                         mask.data_ptr(), fake.data_ptr(), ctx.stream), "s2v_gani_blend")
+        return color, mask, fake
+
+    @torch.no_grad()
+    def forward(self, img, au):
+        """img [B,3,H,W] fp32, au [B,17] -> (color_top, au_top, embed_features), NCHW (model_utils.py:474-482)."""
+        _need_cuda(img, au)
+        b, c, h, w = img.shape
+        if c != 3 or tuple(au.shape) != (b, ganimation_arch.AUS_NC):
+            raise RuntimeError(f"SplitGenerator: expected img [B,3,H,W] and au [B,17], got {tuple(img.shape)} and "
+                               f"{tuple(au.shape)}")
+        ganimation_arch.check_input(h, w)
+        eng, ctx = self._engine(img.device)
+        x20 = NHWC.empty(b, h, w, 3 + ganimation_arch.AUS_NC, img.device)
+        x20.t[..., 3:] = au.float()[:, None, None, :]
+        ops.nchw_to_nhwc(ctx, img.float(), x20.slice(0, 3))
+        head, embed = self._guarded(ctx, lambda: eng.forward(ctx, x20))
+        color, mask, _ = self.blend(ctx, head, x20)
+        emb = torch.empty((b, embed.c, h, w), device=img.device)
+        return color, mask, ops.nhwc_to_nchw(ctx, embed, emb)
+
+
 class ReconNetWrapper(_EngineMixin, face3d_arch.ReconNetWrapperParams):
     """third_part/face3d/models/networks.py:66-105 with net_recon='resnet50', use_last_fc=False (the
     configuration load_face3d_net builds, futils/inference_utils.py:261-267)."""
@@ -508,6 +554,20 @@ def load_fan(path, num_modules=4):
     return net.eval()
 
 
+def load_ganimation(path):
+    """BaseModel.load_ckpt (ganimation_replicate/model/base_model.py:116-138) for net_gen: the state_dict of
+    ``path`` (checkpoints/30_net_gen.pth), a ``module.`` prefix stripped, keys the network does not have
+    dropped (:133); a key the network has and the file lacks raises, as does a missing file.  eval mode."""
+    net = SplitGenerator()
+    sd = _load(path)
+    if isinstance(sd, dict) and "state_dict" in sd:
+        sd = sd["state_dict"]
+    own = net.state_dict()
+    sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
+    net.load_state_dict({k: v for k, v in sd.items() if k in own}, strict=True)
+    return net.eval()
+
+
 def load_face3d_net(ckpt_path, device):
     """futils/inference_utils.py:261-267: ReconNetWrapper('resnet50') with checkpoint['net_recon'],
     strict, eval, on ``device``."""
@@ -526,4 +586,5 @@ def load_srmodel(path, scale=2, num_feat=32):
 
 __all__ = ["LNet", "ENet", "DNet", "GFPGANv1Clean", "FullGenerator", "ParseNet", "RRDBNet", "load_checkpoint",
            "load_network", "load_DNet", "load_gfpgan", "load_gpen", "load_parsenet", "load_srmodel", "RetinaFace",
-           "load_retinaface", "ReconNetWrapper", "define_net_recon", "load_face3d_net", "FAN", "load_fan"]
+           "load_retinaface", "ReconNetWrapper", "define_net_recon", "load_face3d_net", "FAN", "load_fan",
+           "SplitGenerator", "load_ganimation"]

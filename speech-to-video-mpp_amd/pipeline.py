@@ -79,7 +79,8 @@ class LipSyncPipeline:
     side streams and noise counters (the models' per-lane ops.Ctx) and its own graph buffers."""
 
     def __init__(self, dnet, enet, device="cuda", batch: int = 16, graph: bool = True, lanes: int = 1,
-                 ref_hook=None, stitch=None):
+                 ref_hook=None, stitch=None, up_face=None, up_face_name: str | None = None,
+                 without_rl1: bool = False):
         self.dnet, self.enet = dnet, enet
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -94,15 +95,32 @@ class LipSyncPipeline:
         # datagen's reference stitch (inference.py:348-364; stitch.Stitcher, or any callable on (uint8 references
         # [b,3,h,w], uint8 original crops [b,h,w,3])); its landmarks go through the host: eager batches only
         self.stitch = stitch
+        # --up_face / --without_rl1 (inference.py:250-253, :269-286): ``up_face`` a ganimation.GANimationModel
+        # and ``up_face_name`` its expression ('sad', 'angry', 'surprise'); ``without_rl1`` composites the
+        # edited originals (the plain originals without ``up_face``) over the upper half of the prediction.
+        # The reference runs the generator even when the composite is off and drops the result: here the
+        # forward is skipped then.  No host step: batches stay on the graph path.
+        self.up_face, self.without_rl1 = up_face, bool(without_rl1)
+        self._aus = None
+        if up_face is not None:
+            from . import ganimation
+            aus = ganimation.exp_aus_dict[ganimation.check_up_face(up_face_name)]      # ValueError before any launch
+            self._aus = aus.repeat(batch, 1).contiguous().to(self.device)             # tar_aus.repeat(B, 1), :278
+        elif up_face_name not in (None, "original"):
+            raise ValueError(f"up_face_name {up_face_name!r} needs the GANimation model (up_face=)")
+        self.up_face_name = up_face_name
         self._runner = None
         self.reruns = 0             # replayed batches run again in bf16x3 after an f16x3 range overflow
 
     @torch.no_grad()
     def run_batch(self, mel: torch.Tensor, src: torch.Tensor, coeff: torch.Tensor, out_u8: torch.Tensor,
-                  lane: int = 0):
+                  lane: int = 0, orig_u8: torch.Tensor | None = None):
         """mel [b,1,80,16], src [b,3,256,256] in [-1,1] (DNet input, trans_image layout), coeff
-        [b,73,26] -> out_u8 [b,3,384,384] (RGB, NCHW)."""
+        [b,73,26] -> out_u8 [b,3,384,384] (RGB, NCHW).  ``orig_u8`` [b,384,384,3]: the reference's
+        img_original (the uint8 face crops at the prediction's size), required with ``without_rl1``."""
         b, _, h, w = src.shape
+        if self.without_rl1 and orig_u8 is None:
+            raise ValueError("without_rl1 composites the original crops into the prediction: pass orig_u8")
         fake = self.dnet(src, coeff, lane=lane)["fake_image"]
         ref_u8 = torch.empty((b, 3, h, w), dtype=torch.uint8, device=self.device)
         face6 = torch.empty((b, 6, h, w), device=self.device)
@@ -117,16 +135,31 @@ class LipSyncPipeline:
         if self.ref_hook is not None or self.stitch is not None:
             ops.S2V.lipsync_inputs_(src.contiguous(), None, ref_u8, face6, gt)
         pred, _ = self.enet(mel, face6, gt, lane=lane)
+        if self.without_rl1:                                           # inference.py:274-288
+            from . import ganimation
+            fake = None
+            if self.up_face is not None:
+                if self._aus.shape[0] < b:
+                    raise ValueError(f"a batch of {b} frames in a pipeline built for batches of {self.batch}")
+                fake = self.up_face.edit(orig_u8, self._aus[:b], lane=lane)
+            ganimation.gani_compose(self.ctx, pred.contiguous(), orig_u8, fake, out_u8)
+            return out_u8
         ops.S2V.to_u8_(pred, out_u8, 0.0, 1.0, 255.0, 0.0)             # inference.py:267, :288
         return out_u8
 
     @torch.no_grad()
     def run(self, mel_chunks: torch.Tensor, src: torch.Tensor, coeffs: torch.Tensor, start: int = 0,
-            stop: int | None = None) -> torch.Tensor:
-        """Frames [start, stop): ``mel_chunks`` indexed absolutely, ``src`` / ``coeffs`` hold only
-        the frames of this range."""
+            stop: int | None = None, orig_u8: torch.Tensor | None = None) -> torch.Tensor:
+        """Frames [start, stop): ``mel_chunks`` indexed absolutely, ``src`` / ``coeffs`` (and ``orig_u8``
+        [n,384,384,3], with ``without_rl1``) hold only the frames of this range."""
         stop = mel_chunks.shape[0] if stop is None else stop
         n = stop - start
+        if self.without_rl1:
+            if orig_u8 is None or orig_u8.dtype != torch.uint8 or tuple(orig_u8.shape) != (n, 384, 384, 3):
+                raise ValueError(f"without_rl1 needs orig_u8: uint8 [{n}, 384, 384, 3] original crops")
+            orig_u8 = orig_u8.contiguous()
+        else:
+            orig_u8 = None                                   # unused: the batches take the plain path
         if not (0 <= start <= stop <= mel_chunks.shape[0]) or src.shape[0] != n or coeffs.shape[0] != n:
             raise ValueError(f"frames [{start}, {stop}) need {n} src frames / coefficient windows and "
                              f"mel windows up to {stop} (got {src.shape[0]}, {coeffs.shape[0]}, {mel_chunks.shape[0]})")
@@ -138,8 +171,9 @@ class LipSyncPipeline:
         for k, b0 in enumerate(range(0, n, self.batch)):
             b1 = min(n, b0 + self.batch)
             m, s, c = mel_chunks[start + b0: start + b1], src[b0:b1], coeffs[b0:b1]
+            o8 = () if orig_u8 is None else (orig_u8[b0:b1],)
             if self.graph and b1 - b0 == self.batch and self.ref_hook is None and self.stitch is None:
-                runner = self._graph_runner(m, s, c)
+                runner = self._graph_runner(m, s, c, *o8)
                 dst = out[b0:b1]
                 lane = runner.next_lane()
 
@@ -149,13 +183,13 @@ class LipSyncPipeline:
                         for f in self._lane_flags(lane):
                             torch.maximum(flags[k:k + 1], f, out=flags[k:k + 1])
                             f.zero_()
-                runner(m, s, c, out_fn=take)
+                runner(m, s, c, *o8, out_fn=take)
                 out.record_stream(runner.streams[(runner.k - 1) % runner.lanes])
                 replayed.append((k, b0, b1))
             else:
                 if runner is not None:
                     runner.join()                 # the eager batch uses lane 0's workspaces
-                self.run_batch(m, s, c, out[b0:b1])   # eager: the modules guard their own forwards
+                self.run_batch(m, s, c, out[b0:b1], 0, *o8)   # eager: the modules guard their own forwards
         if runner is not None:
             runner.join()
         if flags is not None and replayed:
@@ -163,14 +197,16 @@ class LipSyncPipeline:
             for k, b0, b1 in replayed:
                 if k in bad:                      # a replayed batch left the f16x3 range: again in bf16x3
                     with ops.precision("bf16x3"):
-                        self.run_batch(mel_chunks[start + b0: start + b1], src[b0:b1], coeffs[b0:b1], out[b0:b1])
+                        self.run_batch(mel_chunks[start + b0: start + b1], src[b0:b1], coeffs[b0:b1], out[b0:b1], 0,
+                                       *(() if orig_u8 is None else (orig_u8[b0:b1],)))
                     self.reruns += 1
         return out
 
     def _lane_flags(self, lane):
         """The f16x3 non-finite flags of lane ``lane`` of both networks (one per module and lane)."""
         fl = []
-        for mdl in (self.dnet, self.enet):
+        gen = getattr(self.up_face, "net_gen", None) if self.without_rl1 else None
+        for mdl in (self.dnet, self.enet) + ((gen,) if gen is not None else ()):
             lanes = mdl.__dict__.get("_s2v_engines", {}).get(str(self.device), (None, {}))[1]
             c = lanes.get(lane)
             f = c.range_flag() if c is not None else None
@@ -178,15 +214,17 @@ class LipSyncPipeline:
                 fl.append(f)
         return fl
 
-    def _graph_runner(self, m, s, c):
+    def _graph_runner(self, m, s, c, *o8):
         """Captured run_batch per lane for full batches (~2,000 launches -> one graph replay each);
-        inputs are copied into a lane's static buffers, its uint8 frames read from its static output."""
+        inputs (with ``without_rl1`` the uint8 originals too) are copied into a lane's static buffers, its
+        uint8 frames read from its static output."""
         if self._runner is None:
             from .runtime import LaneRunner
             bufs = [torch.empty((self.batch, 3, 384, 384), dtype=torch.uint8, device=self.device)
                     for _ in range(self.lanes)]
-            self._runner = LaneRunner(lambda lane, mm, ss, cc: self.run_batch(mm, ss, cc, bufs[lane], lane=lane),
-                                      [m.contiguous(), s.contiguous(), c.contiguous()], lanes=self.lanes, warmup=1)
+            self._runner = LaneRunner(lambda lane, mm, ss, cc, *oo: self.run_batch(mm, ss, cc, bufs[lane], lane, *oo),
+                                      [m.contiguous(), s.contiguous(), c.contiguous()] + [o.contiguous() for o in o8],
+                                      lanes=self.lanes, warmup=1)
         return self._runner
 
 

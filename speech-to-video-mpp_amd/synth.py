@@ -194,6 +194,12 @@ def s3fd_state_dict(module):
 # hash-noise crop; tests/golden/make_fan_golden.py asserts the range).
 FAN_SYNTH = dict(gain=0.8)
 
+# GANimation's SplitGenerator: every conv but the two heads is followed by an affine-free instance norm, so
+# the features stay unit-scale whatever the gain; at gain 1.0 the 7x7 heads give O(1) logits (colour std
+# ~0.95, mask std ~0.6, max |logit| 2..4 on hash-noise inputs of 32x32 .. 128x128): tanh and sigmoid stay
+# unsaturated, so a wrong logit moves the masks (tests/golden/make_ganimation_golden.py asserts the range).
+GANIMATION_SYNTH = dict(gain=1.0)
+
 
 # ----------------------------------------------------------------------------- inputs
 def hash_array(key: str, shape, lo: float = -1.0, hi: float = 1.0) -> np.ndarray:
