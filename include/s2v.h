@@ -101,7 +101,14 @@ typedef struct s2v_conv_params {
      *                    ah = bf16(a), al = bf16(a - ah); <= 3*2^-16 relative error per product, any range;
      *   S2V_PREC_F16X3   the same split on v_mfma_f32_32x32x16_f16 (ah = f16(a), al = f16(a - ah)):
      *                    <= 3*2^-22 relative per product for operands in the f16 normal range
-     *                    (|a| < 65504; smaller values keep an absolute error <= 2^-25).
+     *                    (|a| < 65504; smaller values keep an absolute error <= 2^-25);
+     *   S2V_PREC_F16     opt-in single pass on the same MFMA, OUTSIDE the fp32 parity bar: a*b ~ f16(a)*f16(b)
+     *                    (both rounded to nearest even, 11 significant bits per operand as TF32 has;
+     *                    (1 + 2^-11)^2 - 1 = 9.8e-4 relative per product), fp32 accumulate.  It reads the
+     *                    S2V_PREC_F16X3 ``wt_x3`` (the hi halves only; same wt_scale / x_scale / nonfinite) and
+     *                    plans exactly as S2V_PREC_F16X3.  conv_igemm_x3 (plain, persistent, grouped) and
+     *                    conv_x3_halo run single-pass; conv_x3_nar, conv_head_x3 and x_split (conv_glds_x3)
+     *                    launches run as S2V_PREC_F16X3, and s2v_conv2d_plan's out11[6] tells which (3 / 2).
      * Packed weights are read from ``wt_x3`` (s2v_split_weights layout of the same precision, the
      * weights multiplied by ``wt_scale`` before the split — a power of two, 0 means 1 — which the
      * kernel divides out of the accumulators exactly); a b_kn matrix is split on the fly. */
@@ -121,7 +128,7 @@ typedef struct s2v_conv_params {
     int out_pool;
     /* x holds the split layout of ``prec`` (s2v_split_act: per pixel and 32-channel block, 32 hi
      * halves then 32 lo halves — the fp32 tensor's bytes and pitch): both operands are staged by
-     * LDS-DMA (conv_glds_x3).  Needs prec BF16X3 / F16X3, a direct zero-padded conv with cin % 32 == 0,
+     * LDS-DMA (conv_glds_x3).  Needs prec BF16X3 / F16X3 (F16: the F16X3 layout), a direct zero-padded conv with cin % 32 == 0,
      * <= 32 taps, packed weights, no in_scale / pre_act, xcs % 4 == 0 and a 16-byte aligned x. */
     int x_split;
     /* optional launch timer of the implicit-GEMM kernels (bench.py's roofline of graph-replayed,
@@ -158,7 +165,7 @@ typedef struct s2v_conv_params {
     const float *dup_src, *dup_bias; float dup_a; int dup_cs, dup_off;
 } s2v_conv_params;
 
-enum { S2V_PREC_F32 = 0, S2V_PREC_BF16X3 = 1, S2V_PREC_F16X3 = 2 };
+enum { S2V_PREC_F32 = 0, S2V_PREC_BF16X3 = 1, S2V_PREC_F16X3 = 2, S2V_PREC_F16 = 3 };
 
 /* Replaces the nn.Conv2d / ConvTranspose2d / Conv1d / Linear calls of models/LNet.py,
  * ENet.py, DNet.py, base_blocks.py, ffc.py, transformer.py (inventory: SURVEY.md App. A). */
@@ -166,7 +173,8 @@ int s2v_conv2d(const s2v_conv_params *p, s2v_stream_t stream);
 size_t s2v_conv2d_ws_bytes(const s2v_conv_params *p);
 /* The launch plan s2v_conv2d would use, as eleven ints (host only, no device needed):
  *   out11 = {BM, BN, WAVES_M, AVEC, CODE, splits, prec, NW, KS, PF, PERSIST}
- * Tile kernels (BM > 0), told apart by AVEC and prec (out11[6]: 0 for the fp32 kernel, else the precision):
+ * Tile kernels (BM > 0), told apart by AVEC and prec (out11[6]: 0 for the fp32 kernel, else the precision the
+ * launch really runs: a S2V_PREC_F16 launch reports 3 where it runs single-pass, 2 where it falls back):
  *   AVEC 0..3, prec 0   conv_igemm<BM,BN,WAVES_M,AVEC,B_KN>, CODE = B_KN.  AVEC is the A-operand mode: 0 direct
  *                       32-channel slices, 1 generic float4 gather, 2 scalar gather, 3 reflect / nearest-x2 rows;
  *   AVEC 0..4, prec > 0 conv_igemm_x3<BM,BN,WAVES_M,NW,KS,PF,AVEC,B_KN,prec-1> (4: buffer loads), CODE = B_KN;

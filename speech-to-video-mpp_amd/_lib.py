@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libs2v.so")
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_TANH, ACT_GELU_TANH = range(6)
 IN_DIRECT, IN_NEAREST_UP2, IN_TRANSPOSED = range(3)
 PAD_ZERO, PAD_REFLECT = range(2)
-PREC_F32, PREC_BF16X3, PREC_F16X3 = range(3)
+PREC_F32, PREC_BF16X3, PREC_F16X3, PREC_F16 = range(4)
 
 _c_int, _c_float, _c_ll, _c_size, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_void_p
 

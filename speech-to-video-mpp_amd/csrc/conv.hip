@@ -339,7 +339,9 @@ extern "C" int s2v_conv2d_group(const s2v_conv_params *ps, int n, s2v_stream_t s
     }
     S2V_REQUIRE(blocks < (1LL << 31), "conv2d_group: too many tiles");
     hipStream_t s = (hipStream_t)stream;
+    // (a group runs the tile kernels only, so S2V_PREC_F16 members all run single-pass: gp.plan[].prec == 3)
     rc = ps[0].prec == S2V_PREC_BF16X3 ? launch_conv_x3_group<0>(gp.cfg, g, dim3((unsigned)blocks), s)
+         : ps[0].prec == S2V_PREC_F16  ? launch_conv_x3_group<2>(gp.cfg, g, dim3((unsigned)blocks), s)
                                        : launch_conv_x3_group<1>(gp.cfg, g, dim3((unsigned)blocks), s);
     if (rc) return rc;
     rc = check_launch("conv2d_group");
@@ -380,7 +382,9 @@ extern "C" int s2v_conv2d(const s2v_conv_params *p, s2v_stream_t stream) {
         return S2V_E_WORKSPACE;
     }
     const ConvArgs a = make_args(p, pl);
-    const bool bf16 = p->prec == S2V_PREC_BF16X3;
+    // pl.prec is the arithmetic the launch really runs: S2V_PREC_F16 on the tile / halo routes, S2V_PREC_F16X3
+    // where that mode falls back (conv_plan.cpp make_plan)
+    const bool bf16 = pl.prec == S2V_PREC_BF16X3, f16s = pl.prec == S2V_PREC_F16;
     dim3 grid;
     if (tiles) grid = dim3(cdiv(pl.M, pl.t.bm), cdiv(pl.cout, pl.t.bn), pl.batch * pl.splits);
     const char *what = "conv_igemm";
@@ -395,7 +399,7 @@ extern "C" int s2v_conv2d(const s2v_conv_params *p, s2v_stream_t stream) {
             what = "conv_smallk";
             break;
         case Route::HeadX3:
-            rc = launch_conv_head_x3(a, p->prec, p->cout, pl.fsize, pl.ncs, pl.rows, s);
+            rc = launch_conv_head_x3(a, pl.prec, p->cout, pl.fsize, pl.ncs, pl.rows, s);
             what = "conv_head_x3";
             break;
         case Route::HaloSmall:
@@ -415,7 +419,9 @@ extern "C" int s2v_conv2d(const s2v_conv_params *p, s2v_stream_t stream) {
             break;
         case Route::X3Halo:                       // one block per (image, patch)
             grid.x = (unsigned)((long long)p->n * cdiv(p->oh, pl.th) * cdiv(p->ow, 64));
-            rc = bf16 ? launch_conv_x3_halo<0>(a, pl.th, pl.wn, grid, s) : launch_conv_x3_halo<1>(a, pl.th, pl.wn, grid, s);
+            rc = bf16   ? launch_conv_x3_halo<0>(a, pl.th, pl.wn, grid, s)
+                 : f16s ? launch_conv_x3_halo<2>(a, pl.th, pl.wn, grid, s)
+                        : launch_conv_x3_halo<1>(a, pl.th, pl.wn, grid, s);
             break;
         case Route::X3Nar:
             rc = bf16 ? launch_conv_x3_nar<0>(a, pl.amode == 7, grid, s) : launch_conv_x3_nar<1>(a, pl.amode == 7, grid, s);
@@ -428,8 +434,9 @@ extern "C" int s2v_conv2d(const s2v_conv_params *p, s2v_stream_t stream) {
                 ap.vgrid_z = (int)grid.z;
                 grid = dim3((unsigned)pl.persist, 1, 1);
             }
-            rc = bf16 ? launch_conv_x3<0>(pl.tile, ap, pl.amode, pl.bkn, grid, s)
-                      : launch_conv_x3<1>(pl.tile, ap, pl.amode, pl.bkn, grid, s);
+            rc = bf16   ? launch_conv_x3<0>(pl.tile, ap, pl.amode, pl.bkn, grid, s)
+                 : f16s ? launch_conv_x3<2>(pl.tile, ap, pl.amode, pl.bkn, grid, s)
+                        : launch_conv_x3<1>(pl.tile, ap, pl.amode, pl.bkn, grid, s);
             break;
         }
         case Route::Igemm:

@@ -5,7 +5,7 @@
 
 namespace s2v {
 
-template <int ELT>   // 0 = bf16, 1 = f16 halves (conv_x3_impl.hpp; instances in conv_x3_{bf16,f16}.hip); 0 or an error
+template <int ELT>   // 0 = bf16, 1 = f16 halves, 2 = single-pass f16 (conv_x3_impl.hpp; instances in conv_x3_{bf16,f16,f16s}.hip); 0 or an error
 int launch_conv_x3(int tile, const ConvArgs &a, int amode, bool bkn, dim3 grid, hipStream_t s);
 template <int ELT>   // LDS-DMA kernels on split-layout inputs (conv_glds.hip): cfg 0 = 256x256, 1 = 256x128, 2 = 512x128
 void launch_conv_glds(int cfg, const ConvArgs &a, dim3 grid, hipStream_t s);
@@ -13,7 +13,7 @@ template <int ELT>   // grouped x3 launches (conv_x3_impl.hpp conv_igemm_x3_grou
 int launch_conv_x3_group(int cfg, const ConvGroup &g, dim3 grid, hipStream_t s);
 template <int ELT>   // narrow-N register-direct-A kernel (conv_x3_nar.hip); breg: B fragments direct too
 int launch_conv_x3_nar(const ConvArgs &a, bool breg, dim3 grid, hipStream_t s);
-template <int ELT>   // 3x3 spatial-patch kernel with the input halo staged once per channel slice (conv_x3_halo.hip)
+template <int ELT>   // 3x3 spatial-patch kernel with the input halo staged once per channel slice (conv_x3_halo_impl.hpp; ELT 0..2)
 int launch_conv_x3_halo(const ConvArgs &a, int th, int wn, dim3 grid, hipStream_t s);
 
 // split-precision Cout <= 4 heads (conv_head.hip): 0 or an error

@@ -509,6 +509,9 @@ static Plan new_plan(const s2v_conv_params *p, int M, int K) {
 // The one place that decides the route and every instance parameter of a validated launch.
 static Plan make_plan(const s2v_conv_params *p_in, int M, int K) {
     s2v_conv_params q = *p_in;
+    // single-pass f16 plans exactly as f16x3 (same route, tile, splits, persistence: the predicates below see
+    // S2V_PREC_F16X3); the plan's prec then says what the launch really runs
+    if (q.prec == S2V_PREC_F16) q.prec = S2V_PREC_F16X3;
     if (q.out_pool) q.force_splits = 1;          // the pooled epilogue needs whole-K tiles
     const s2v_conv_params *p = &q;
     Plan pl = new_plan(p, M, K);
@@ -548,6 +551,9 @@ static Plan make_plan(const s2v_conv_params *p_in, int M, int K) {
         make_plan_igemm(p, pl);
     }
     if (pl.splits > 1) pl.ws_bytes = (size_t)pl.batch * pl.splits * (size_t)M * p->cout * sizeof(float);
+    // the families with single-pass (ELT 2) instances: conv_igemm_x3 (plain / persistent) and conv_x3_halo; every
+    // other split-precision family (conv_x3_nar, conv_head_x3, conv_glds_x3) runs the mode as f16x3
+    if (p_in->prec == S2V_PREC_F16 && (pl.route == Route::X3Tile || pl.route == Route::X3Halo)) pl.prec = S2V_PREC_F16;
     return pl;
 }
 
@@ -564,7 +570,8 @@ static int validate(const s2v_conv_params *p, int &M, int &K) {
     S2V_REQUIRE(!p->stamps || (p->stamp_ctr && p->stamp_reps > 0 && p->stamp_slot >= 0 &&
                                p->stamp_slot < p->stamp_stride),
                 "conv2d: launch stamps need stamp_ctr, stamp_reps > 0 and 0 <= stamp_slot < stamp_stride");
-    S2V_REQUIRE(p->prec == S2V_PREC_F32 || p->prec == S2V_PREC_BF16X3 || p->prec == S2V_PREC_F16X3,
+    S2V_REQUIRE(p->prec == S2V_PREC_F32 || p->prec == S2V_PREC_BF16X3 || p->prec == S2V_PREC_F16X3 ||
+                    p->prec == S2V_PREC_F16,
                 "conv2d: bad prec %d", p->prec);
     S2V_REQUIRE(pow2_or_zero(p->wt_scale), "conv2d: wt_scale must be 0 or a positive power of two, got %g", p->wt_scale);
     const bool x3 = tiled_x3(p);
@@ -587,7 +594,8 @@ static int validate(const s2v_conv_params *p, int &M, int &K) {
                     cdiv(p->cout, t.bn) * t.bn, p->npad);
     }
     if (p->x_split) {
-        S2V_REQUIRE(p->prec == S2V_PREC_BF16X3 || p->prec == S2V_PREC_F16X3, "conv2d: x_split needs prec BF16X3 / F16X3");
+        S2V_REQUIRE(p->prec == S2V_PREC_BF16X3 || p->prec == S2V_PREC_F16X3 || p->prec == S2V_PREC_F16,
+                    "conv2d: x_split needs prec BF16X3 / F16X3");
         S2V_REQUIRE(!p->b_kn && p->in_mode == S2V_IN_DIRECT && p->pad_mode == S2V_PAD_ZERO && p->cin % 32 == 0 &&
                         p->kh * p->kw <= 32 && !p->in_scale && p->pre_act == S2V_ACT_NONE && p->xcs % 4 == 0 &&
                         ((uintptr_t)p->x % 16) == 0 && p->x_bs % 4 == 0 && p->force_tile == 0,

@@ -14,6 +14,10 @@
 //          activations (|v| << 65504 on every path of this model family).
 // Both cost three 16-bit MFMAs (96 cycles per 32x32x16 block against 512 for eight
 // v_mfma_f32_32x32x2_f32) and the same VALU work to split an operand (v_cvt_pk_{bf16,f16}_f32 ...).
+//   ELT 2, single-pass f16 (S2V_PREC_F16, opt-in, outside the fp32 parity bar): the hi halves of ELT 1
+//          alone, one MFMA per fragment pair: a product is f16(a) * f16(b), (1 + 2^-11)^2 - 1 relative.
+//          The lo halves of A are neither computed, stored to LDS nor read; B is the ELT 1 weight layout
+//          (whole rows staged, lo slots unread).  Same LDS rows, swizzle, K order and epilogues.
 //
 // Same GEMM view, gather loaders, K-slice order, XCD-aware tile order and epilogue as the fp32
 // kernel (conv.hip / conv_impl.hpp).  Differences:
@@ -48,6 +52,9 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #ifndef X3_F16_MIX
 #define X3_F16_MIX 1
 #endif
+
+// ELT 2: hi halves only, one MFMA per fragment pair
+constexpr bool x3_single(int elt) { return elt == 2; }
 
 // two fp32 -> two 16-bit halves of type ELT (RNE): v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32
 template <int ELT>
@@ -98,6 +105,12 @@ __device__ __forceinline__ void split4(const f4 &v, u32x2 &hi, u32x2 &lo) {
         lo.x = pack2<ELT>(v.x - h0, v.y - h1);
         lo.y = pack2<ELT>(v.z - h2, v.w - h3);
     }
+}
+
+// 4 fp32 -> 4 hi halves (the single-pass operand)
+template <int ELT>
+__device__ __forceinline__ u32x2 hi4(const f4 &v) {
+    return u32x2{pack2<ELT>(v.x, v.y), pack2<ELT>(v.z, v.w)};
 }
 
 // Main-loop MFMA shape: 16x16x32 (default) or 32x32x16 (X3_MFMA16=0).  Same FLOP per cycle and
@@ -152,11 +165,15 @@ __device__ __forceinline__ void store_a_x3(char *As, int tid, const f4 (&ra)[AR]
 #pragma unroll
     for (int j = 0; j < AR; ++j) {
         const int row = ar + RS * j;
-        u32x2 hi, lo;
-        split4<ELT>(ra[j], hi, lo);
         const int off = slot_off(row, q >> 1) + (q & 1) * 8;
-        *(u32x2 *)(As + off) = hi;
-        *(u32x2 *)(As + (off ^ 64)) = lo;          // slot ^ 4 == the lo slot (slot < 4)
+        if constexpr (x3_single(ELT)) {
+            *(u32x2 *)(As + off) = hi4<ELT>(ra[j]);
+        } else {
+            u32x2 hi, lo;
+            split4<ELT>(ra[j], hi, lo);
+            *(u32x2 *)(As + off) = hi;
+            *(u32x2 *)(As + (off ^ 64)) = lo;          // slot ^ 4 == the lo slot (slot < 4)
+        }
     }
 }
 
@@ -175,13 +192,18 @@ __device__ __forceinline__ void store_a8_x3(char *As, int tid, const f4 (&ra)[2 
     const int q = tid & 3;
 #pragma unroll
     for (int j = 0; j < AR8; ++j) {
-        u32x2 h0, l0, h1, l1;
-        split4<ELT>(ra[2 * j], h0, l0);
-        split4<ELT>(ra[2 * j + 1], h1, l1);
-        const u32x4 hi = {h0.x, h0.y, h1.x, h1.y}, lo = {l0.x, l0.y, l1.x, l1.y};
         const int off = slot_off(a_row8<NT>(tid, j), q);
-        *(u32x4 *)(As + off) = hi;
-        *(u32x4 *)(As + (off ^ 64)) = lo;
+        if constexpr (x3_single(ELT)) {
+            const u32x2 h0 = hi4<ELT>(ra[2 * j]), h1 = hi4<ELT>(ra[2 * j + 1]);
+            *(u32x4 *)(As + off) = u32x4{h0.x, h0.y, h1.x, h1.y};
+        } else {
+            u32x2 h0, l0, h1, l1;
+            split4<ELT>(ra[2 * j], h0, l0);
+            split4<ELT>(ra[2 * j + 1], h1, l1);
+            const u32x4 hi = {h0.x, h0.y, h1.x, h1.y}, lo = {l0.x, l0.y, l1.x, l1.y};
+            *(u32x4 *)(As + off) = hi;
+            *(u32x4 *)(As + (off ^ 64)) = lo;
+        }
     }
 }
 
@@ -211,15 +233,16 @@ __device__ __forceinline__ void store_b_kn_x3(char *Bs, int tid, const f4 (&rb)[
 #pragma unroll
     for (int j = 0; j < BR; ++j) {
         const int k = kr + RPP * j;
-        u32x2 hi, lo;
-        split4<ELT>(rb[j], hi, lo);
+        u32x2 hi, lo = {0u, 0u};
+        if constexpr (x3_single(ELT)) hi = hi4<ELT>(rb[j]);
+        else split4<ELT>(rb[j], hi, lo);
         const unsigned hs[4] = {hi.x & 0xffffu, hi.x >> 16, hi.y & 0xffffu, hi.y >> 16};
         const unsigned ls[4] = {lo.x & 0xffffu, lo.x >> 16, lo.y & 0xffffu, lo.y >> 16};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int off = slot_off(nn + e, k >> 3) + (k & 7) * 2;
             *(unsigned short *)(Bs + off) = (unsigned short)hs[e];
-            *(unsigned short *)(Bs + (off ^ 64)) = (unsigned short)ls[e];
+            if constexpr (!x3_single(ELT)) *(unsigned short *)(Bs + (off ^ 64)) = (unsigned short)ls[e];
         }
     }
 }
@@ -533,15 +556,16 @@ __device__ __forceinline__ void conv_x3_tile(const ConvArgs &a, int L, int gx, i
                 u32x4 bh[TN16], bl[TN16];
                 u32x4 ah[X3_APIPE ? 2 : 1], al[X3_APIPE ? 2 : 1];
                 const char *pa = As + (wm * WTM + l16) * 128;
+                constexpr bool LO = !x3_single(ELT);     // the lo fragments and their two MFMAs
                 if constexpr (X3_APIPE) {
                     ah[0] = *(const u32x4 *)(pa + hs16);
-                    al[0] = *(const u32x4 *)(pa + ls16);
+                    if constexpr (LO) al[0] = *(const u32x4 *)(pa + ls16);
                 }
 #pragma unroll
                 for (int j = 0; j < TN16; ++j) {
                     const char *p = Bs + (wn * WTN + j * 16 + l16) * 128;
                     bh[j] = *(const u32x4 *)(p + hs16);
-                    bl[j] = *(const u32x4 *)(p + ls16);
+                    if constexpr (LO) bl[j] = *(const u32x4 *)(p + ls16);
                 }
 #pragma unroll
                 for (int i = 0; i < TM16; ++i) {
@@ -549,16 +573,18 @@ __device__ __forceinline__ void conv_x3_tile(const ConvArgs &a, int L, int gx, i
                     if constexpr (X3_APIPE) {
                         if (i + 1 < TM16) {
                             ah[c ^ 1] = *(const u32x4 *)(pa + (i + 1) * 16 * 128 + hs16);
-                            al[c ^ 1] = *(const u32x4 *)(pa + (i + 1) * 16 * 128 + ls16);
+                            if constexpr (LO) al[c ^ 1] = *(const u32x4 *)(pa + (i + 1) * 16 * 128 + ls16);
                         }
                     } else {
                         ah[0] = *(const u32x4 *)(pa + i * 16 * 128 + hs16);
-                        al[0] = *(const u32x4 *)(pa + i * 16 * 128 + ls16);
+                        if constexpr (LO) al[0] = *(const u32x4 *)(pa + i * 16 * 128 + ls16);
                     }
 #pragma unroll
                     for (int j = 0; j < TN16; ++j) {
-                        acc4[i][j] = mfma16x16<ELT>(al[c], bh[j], acc4[i][j]);
-                        acc4[i][j] = mfma16x16<ELT>(ah[c], bl[j], acc4[i][j]);
+                        if constexpr (LO) {
+                            acc4[i][j] = mfma16x16<ELT>(al[c], bh[j], acc4[i][j]);
+                            acc4[i][j] = mfma16x16<ELT>(ah[c], bl[j], acc4[i][j]);
+                        }
                         acc4[i][j] = mfma16x16<ELT>(ah[c], bh[j], acc4[i][j]);
                     }
                 }
@@ -572,20 +598,22 @@ __device__ __forceinline__ void conv_x3_tile(const ConvArgs &a, int L, int gx, i
                 for (int i = 0; i < TM; ++i) {
                     const char *p = As + (wm * WTM + i * 32 + li) * 128;
                     ah[i] = *(const u32x4 *)(p + hs);
-                    al[i] = *(const u32x4 *)(p + ls);
+                    if constexpr (!x3_single(ELT)) al[i] = *(const u32x4 *)(p + ls);
                 }
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const char *p = Bs + (wn * WTN + j * 32 + li) * 128;
                     bh[j] = *(const u32x4 *)(p + hs);
-                    bl[j] = *(const u32x4 *)(p + ls);
+                    if constexpr (!x3_single(ELT)) bl[j] = *(const u32x4 *)(p + ls);
                 }
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
-                        acc[i][j] = mfma16<ELT>(al[i], bh[j], acc[i][j]);
-                        acc[i][j] = mfma16<ELT>(ah[i], bl[j], acc[i][j]);
+                        if constexpr (!x3_single(ELT)) {
+                            acc[i][j] = mfma16<ELT>(al[i], bh[j], acc[i][j]);
+                            acc[i][j] = mfma16<ELT>(ah[i], bl[j], acc[i][j]);
+                        }
                         acc[i][j] = mfma16<ELT>(ah[i], bh[j], acc[i][j]);
                     }
             }
@@ -758,7 +786,7 @@ static bool launch_x3(const ConvArgs &a, int amode, bool bkn, dim3 grid, hipStre
 // layers; conv.hip only sets a.vgrid_* for that configuration)
 constexpr bool x3_has_persist(int cfg, int amode, bool bkn) { return cfg == 0 && amode == 4 && !bkn; }
 
-// The tile configurations are instantiated in three parts (conv_x3_{f16,bf16}{,_1,_2}.hip) so the six
+// The tile configurations are instantiated in three parts (conv_x3_{f16,bf16,f16s}{,_1,_2}.hip) so the nine
 // translation units compile in parallel: part 0 = configurations 0 - 5, 1 = 6 - 11, 2 = 12 - 14.
 template <int ELT, int PART>
 bool launch_conv_x3_part(int cfg, const ConvArgs &a, int amode, bool bkn, dim3 grid, hipStream_t s) {

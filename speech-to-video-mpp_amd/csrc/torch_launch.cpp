@@ -273,6 +273,9 @@ std::vector<int64_t> group_end_(const OptT &ws, bool dry) {
     return {0, grouped ? 1 : 0};
 }
 
+// the weight / activation layout a precision reads: single-pass f16 shares f16x3's (hi halves only)
+static int split_layout(int64_t prec) { return prec == S2V_PREC_F16 ? S2V_PREC_F16X3 : (int)prec; }
+
 // Implicit-GEMM convolution (s2v_conv_params, include/s2v.h) with packed weights [npad][kpad]
 // (and, for the split precisions, their s2v_split_weights copy).  Returns [ws_need, plan...]:
 // ws_need 0 = launched (or dry run of a launch that needs no workspace); > 0 = bytes of workspace
@@ -426,7 +429,7 @@ std::vector<int64_t> modulated_conv2d_(const Tensor &x, const Tensor &y, const T
     if (x3) {
         // demodulated rows have |w * s * d| <= post (sqrt 2 on these paths): f16 halves take a fixed 2^11
         // pre-scale; without demodulation the range is open and the weights go unscaled
-        wscale = (prec == S2V_PREC_F16X3 && has(d)) ? 2048.f : 1.f;
+        wscale = ((prec == S2V_PREC_F16X3 || prec == S2V_PREC_F16) && has(d)) ? 2048.f : 1.f;
         p.wt = nullptr; p.wt_x3 = wbuf.data_ptr(); p.wt_scale = wscale;
     }
     set_stamps(p, stamps, stamp_ctr, stamp_pos, dev);
@@ -444,7 +447,7 @@ std::vector<int64_t> modulated_conv2d_(const Tensor &x, const Tensor &y, const T
                 x3 ? "split, pre-scale " : "fp32", x3 ? wscale : 0.f, ")");
     if (premod == 0.0 && x3)
         check(s2v_modulate_weights_split(wt.data_ptr<float>(), npad, kpad, K, p.cin, (int)cout, s.data_ptr<float>(),
-                                         s_ns, dp, d_ns, B, (int)prec, wscale, wbuf.data_ptr(), stream()),
+                                         s_ns, dp, d_ns, B, split_layout(prec), wscale, wbuf.data_ptr(), stream()),
               "s2v_modulate_weights_split");
     else if (premod == 0.0)
         check(s2v_modulate_weights(wt.data_ptr<float>(), npad, kpad, K, p.cin, (int)cout, s.data_ptr<float>(), s_ns, dp,

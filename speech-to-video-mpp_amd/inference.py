@@ -373,7 +373,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         ref_hook=None, restore: bool = True, restorer=None, enhancer=None, face_det: bool = False,
         pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None,
         landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None,
-        up_face: str = "original", without_rl1: bool = False, up_face_model=None):
+        up_face: str = "original", without_rl1: bool = False, up_face_model=None, precision: str | None = None):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -396,8 +396,15 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     ``up_face`` ('original', 'sad', 'angry', 'surprise') / ``without_rl1``: GANimation's upper-face edit and the
     composite of inference.py:269-286 (``up_face_model``: an initialised ganimation.GANimationModel, else one
     over ``ckpt_dir``/30_net_gen.pth or the synthetic preset); ``meta`` gains ``up_face``, ``without_rl1`` and
-    ``up_face_weights``."""
-    from . import audio, pipeline, post, synth
+    ``up_face_weights``.  ``precision``: the conv arithmetic of the whole clip (an ops.set_precision name; None
+    leaves ops.PRECISION alone), restored afterwards; ``meta["conv_arith"]`` names the arithmetic that ran.  The
+    opt-in "f16" (single-pass f16 products) is outside the fp32 parity bar: about 0.5 grey level on average."""
+    kw = dict(locals())                                     # the arguments (nothing else is bound yet)
+    from . import audio, ops, pipeline, post, synth
+    if precision is not None:
+        kw["precision"] = None
+        with ops.precision(precision):                      # ValueError on a bad name before anything runs
+            return run(**kw)
     if up_face != "original":
         from . import ganimation
         ganimation.check_up_face(up_face)                  # ValueError before anything runs
@@ -500,7 +507,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
             "mel_cols": int(mel.shape[1]), "mel_windows": int(chunks.shape[0]), "wav_samples_16k": int(len(wav)),
             "box": [y1, y2, x1, x2], "semantic": skind, "ref_enhance": ref_hook is not None,
             "restore": bool(enhance and restore), "up_face": up_face, "without_rl1": bool(without_rl1),
-            "up_face_weights": ukind,
+            "up_face_weights": ukind, "conv_arith": ops.PRECISION,
             "seconds": round(time.time() - t0, 3)}
     if face_det:
         meta["boxes"] = [list(b) for b in boxes]
@@ -547,6 +554,10 @@ def build_parser():
     ap.add_argument("--without_rl1", default=False, action="store_true",
                     help="composite the (edited) original crop over the prediction wherever the masked input was "
                          "not zero: the upper half of the face")
+    ap.add_argument("--precision", default=None, choices=["f16x3", "bf16x3", "f32", "f16"],
+                    help="conv arithmetic of the whole clip (default: the process setting, S2V_PRECISION or f16x3); "
+                         "f16 is the fast single-pass mode, OUTSIDE the fp32 parity bar (about 0.5 grey level on "
+                         "average, 3-5 at the worst pixel)")
     return ap
 
 
@@ -557,7 +568,7 @@ def main(argv=None):
     r = run(a.face, a.audio, a.max_frames, a.LNet_batch_size, a.box_frac, a.checkpoints, a.enhance,
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
             nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
-            stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1)
+            stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1, precision=a.precision)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     arrays = {"frames": r["frames"].cpu().numpy(), "preds": r["preds"].cpu().numpy()}
     if r["enhanced"] is not None:

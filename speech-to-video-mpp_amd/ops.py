@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, torch_ops
 from ._lib import (ACT_GELU_TANH, ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH,  # noqa: F401
-                   IN_DIRECT, IN_NEAREST_UP2, IN_TRANSPOSED, PAD_REFLECT, PAD_ZERO, PREC_BF16X3, PREC_F16X3, PREC_F32,
+                   IN_DIRECT, IN_NEAREST_UP2, IN_TRANSPOSED, PAD_REFLECT, PAD_ZERO, PREC_BF16X3, PREC_F16, PREC_F16X3, PREC_F32,
                    check)
 
 F32 = 4
@@ -34,10 +34,14 @@ F32 = 4
 #            into it by a power of two, undone exactly in the epilogue);
 #   "bf16x3" split-fp32 on the bf16 MFMA: 16 significant bits per operand, <= 3*2^-16 per product,
 #            any fp32 range;
-#   "f32"    exact fp32 MFMA.
-# All three run fp32 tensors with fp32 accumulation.  The S2V_PRECISION environment variable sets
+#   "f32"    exact fp32 MFMA;
+#   "f16"    opt-in single pass on the f16 MFMA, OUTSIDE the fp32 parity bar: each product is f16(a) * f16(b)
+#            (11 significant bits per operand, the class of TF32; 9.8e-4 relative per product).  It reads the
+#            f16x3 weight layout, pre-scales and range guard (hi halves only) and plans as f16x3; kernel
+#            families without a single-pass instance run as f16x3.
+# All four run fp32 tensors with fp32 accumulation.  The S2V_PRECISION environment variable sets
 # the process default; set_precision() changes it.
-_PRECISIONS = {"f16x3": PREC_F16X3, "bf16x3": PREC_BF16X3, "f32": PREC_F32}
+_PRECISIONS = {"f16x3": PREC_F16X3, "bf16x3": PREC_BF16X3, "f32": PREC_F32, "f16": PREC_F16}
 SPLIT_PRECISIONS = ("f16x3", "bf16x3")
 PRECISION = os.environ.get("S2V_PRECISION", "f16x3")
 if PRECISION not in _PRECISIONS:
@@ -72,7 +76,7 @@ def x_scale_for(amax: float) -> float:
 
 
 def set_precision(name: str) -> str:
-    """Select the conv arithmetic ("f16x3", "bf16x3" or "f32") for launches issued from now on; returns the
+    """Select the conv arithmetic ("f16x3", "bf16x3", "f32" or the opt-in single-pass "f16") for launches issued from now on; returns the
     previous setting.  A captured HIP graph keeps the precision it was captured with."""
     global PRECISION
     if name not in _PRECISIONS:
@@ -93,6 +97,12 @@ def precision(name: str):
 
 def prec_code() -> int:
     return _PRECISIONS[PRECISION]
+
+
+def layout_code(prec: int) -> int:
+    """The precision code whose weight / activation layout, pre-scales and fused kernels ``prec`` uses:
+    single-pass f16 shares everything of f16x3 (it reads the hi halves)."""
+    return PREC_F16X3 if prec == PREC_F16 else prec
 
 # Optional per-launch observer (bench.py's live roofline): called as hook(ctx, info, flops, launch)
 # where info is the launch's ConvLaunch (kernel plan + shape) and launch() performs the conv; the
@@ -428,7 +438,7 @@ class ConvW:
         """Power-of-two pre-scale of the split weights (s2v_conv_params.wt_scale): f16 halves get
         max|W| into [2^13, 2^14) so every weight and its lo half stay in the f16 normal range; bf16
         has fp32's exponent range and needs none."""
-        if prec != PREC_F16X3:
+        if layout_code(prec) != PREC_F16X3:
             return 1.0
         if getattr(self, "_f16_scale", None) is None:
             m = float(self.wt.abs().max())
@@ -437,6 +447,7 @@ class ConvW:
 
     def wt_x3(self, ctx: "Ctx", prec: int = PREC_BF16X3) -> torch.Tensor:
         """The packed weights in the split layout of ``prec`` (built once per precision, on first use)."""
+        prec = layout_code(prec)               # "f16" reads the f16x3 copy: no second cache entry
         if self._split is None:
             self._split = {}
         if prec not in self._split:
@@ -612,7 +623,7 @@ def _conv(ctx, x, cw, yv, out_step, act, alpha, resv, res_after, res_offset, nc_
     parity-class view of a wider tensor)."""
     prec = prec_code()
     x_split = int(getattr(x, "split", 0))
-    if x_split and x_split != prec:
+    if x_split and x_split != layout_code(prec):
         raise _lib.S2VError(f"conv: the input holds the split layout of precision code {x_split}, but the conv runs "
                             f"in {PRECISION!r} (code {prec}); split it again with split_act after set_precision")
     wsplit = cw.wt_x3(ctx, prec) if prec != PREC_F32 else None
@@ -624,7 +635,7 @@ def _conv(ctx, x, cw, yv, out_step, act, alpha, resv, res_after, res_offset, nc_
     key = None
     if (PERFDB or TUNE is not None) and prec != PREC_F32 and not (force_tile or force_splits or x_split or cap or
                                                                    _grouping()):
-        key = conv_key(x, cw, yv, out_step, pool, prec)
+        key = conv_key(x, cw, yv, out_step, pool, layout_code(prec))      # an f16x3 entry serves "f16" unchanged
         if TUNE is None and perfdb_applies(x.t.device):
             force_tile, force_splits = PERFDB.get(key, (0, 0))
 
@@ -681,8 +692,8 @@ def check_all_ranges(what="s2v"):
 
 
 def guard_active() -> bool:
-    """The f16x3 range guard applies to launches issued now."""
-    return RANGE_GUARD and PRECISION == "f16x3"
+    """The f16 range guard (f16x3 and single-pass f16) applies to launches issued now."""
+    return RANGE_GUARD and PRECISION in ("f16x3", "f16")
 
 
 class _Calibration:
@@ -774,7 +785,7 @@ def _range(ctx, cw, x, prec, in_scale=None):
     """(x_scale, flag) of an f16x3 launch: the layer's calibrated activation pre-scale and the lane's
     non-finite flag.  An uncalibrated layer is measured: into the lane's calibration buffer during a
     calibration forward (launched unscaled), else on the spot with one host sync."""
-    if prec != PREC_F16X3 or not RANGE_GUARD or int(getattr(x, "split", 0)):
+    if layout_code(prec) != PREC_F16X3 or not RANGE_GUARD or int(getattr(x, "split", 0)):
         return 1.0, None
     scales = cw.__dict__.setdefault("_xscale", {})
     s = scales.get(prec)
@@ -832,8 +843,8 @@ def modulate_weights(ctx: Ctx, cw: ConvW, s: torch.Tensor, d: torch.Tensor | Non
     side stream as soon as the style code exists)."""
     prec = prec_code()
     wbuf = empty((batch, cw.npad, cw.kpad), cw.wt.device)      # (calling-stream memory on a side branch)
-    wscale = 2048.0 if (prec == PREC_F16X3 and d is not None) else 1.0
-    S2V.modulate_weights_(cw.wt, s, d, wbuf, cw.cout, cw.cin, cw.kh * cw.kw, prec, wscale)
+    wscale = 2048.0 if (layout_code(prec) == PREC_F16X3 and d is not None) else 1.0
+    S2V.modulate_weights_(cw.wt, s, d, wbuf, cw.cout, cw.cin, cw.kh * cw.kw, layout_code(prec), wscale)
     return wbuf, (wscale if prec != PREC_F32 else -1.0)
 
 
@@ -864,14 +875,14 @@ def modulated_conv2d(ctx: Ctx, x: NHWC, cw: ConvW, y: NHWC, s: torch.Tensor, d: 
     yv, resv = y.v, None if res is None else res.v
     prec = prec_code()
     x_split = int(getattr(x, "split", 0))
-    if x_split and x_split != prec:
+    if x_split and x_split != layout_code(prec):
         raise _lib.S2VError(f"modulated conv: the input holds the split layout of precision code {x_split}, but the "
                             f"conv runs in {PRECISION!r} (code {prec})")
     sh = cw.shift if shift is None else shift            # the layer bias (epilogue shift) unless overridden
     xscale, flag = _range(ctx, cw, x, prec)
     key, force_tile = None, 0
     if (PERFDB or TUNE is not None) and prec != PREC_F32 and not (force_splits or x_split):
-        key = conv_key(x, cw, yv, 1, False, prec) + f"|mod{int(d is not None)}{int(d2s)}"
+        key = conv_key(x, cw, yv, 1, False, layout_code(prec)) + f"|mod{int(d is not None)}{int(d2s)}"
         if TUNE is None and perfdb_applies(x.t.device):
             force_tile, force_splits = PERFDB.get(key, (0, 0))
 
@@ -945,8 +956,8 @@ def conv_symbol(ctx: Ctx, p) -> str:
 def split_act(ctx: Ctx, x: NHWC, out: NHWC | None = None) -> NHWC:
     """fp32 activations -> the split layout of the current precision (``s2v::split_act_``), the
     input form of the LDS-DMA convolutions.  ``out``: a whole contiguous tensor of x's shape."""
-    prec = prec_code()
-    assert prec != PREC_F32, "split_act needs a split precision (f16x3 / bf16x3)"
+    prec = layout_code(prec_code())
+    assert prec != PREC_F32, "split_act needs a split precision (f16x3 / bf16x3 / f16)"
     if out is None:
         out = NHWC.empty(x.n, x.h, x.w, x.c, x.t.device)
     assert (out.n, out.h, out.w, out.c) == (x.n, x.h, x.w, x.c) and out.coff == 0
@@ -1271,13 +1282,13 @@ def fft_tables(h: int, w: int, device):
 def ffc_fused_ok() -> bool:
     """The fused LNet FFC kernels (s2v_ffc_*) cover the split-precision arithmetic; exact f32 runs the
     separate st1 / rfft2 / fu / irfft2 / st2 / instnorm launches."""
-    return PRECISION in ("f16x3", "bf16x3")
+    return PRECISION in ("f16x3", "bf16x3", "f16")       # "f16": the fused kernels run as f16x3
 
 
 def ffc_spec_fwd(ctx: Ctx, xg: NHWC, cw: ConvW, tables: torch.Tensor, t1: NHWC, spec: torch.Tensor):
     """t1 = relu(bn1(x_g conv1)), spec = rfftn(t1, ortho) in one launch (s2v_ffc_spec_fwd): ffc.py:98-104,
     :158-160 (SpectralTransform.conv1 + FourierUnit's rfftn)."""
-    prec = prec_code()
+    prec = layout_code(prec_code())
     xs, flag = _range(ctx, cw, xg, prec)
     S2V.ffc_spec_fwd_(xg.v, cw.wt_x3(ctx, prec), cw.split_scale(prec), xs, cw.scale, cw.shift, tables, t1.v, spec,
                       flag, prec)
@@ -1287,7 +1298,7 @@ def ffc_spec_fwd(ctx: Ctx, xg: NHWC, cw: ConvW, tables: torch.Tensor, t1: NHWC, 
 def ffc_spec_inv(ctx: Ctx, spec: torch.Tensor, cw: ConvW, tables: torch.Tensor, t1: NHWC, u: NHWC):
     """u = irfftn(relu(bn_fu(spec conv_fu)), ortho) + t1 in one launch (s2v_ffc_spec_inv): ffc.py:106-126,
     :162 (FourierUnit conv + irfftn, SpectralTransform's x + fu(x))."""
-    prec = prec_code()
+    prec = layout_code(prec_code())
     b, f, c2 = spec.shape
     xs, flag = _range(ctx, cw, NHWC(spec.view(b, f, 1, c2)), prec)
     S2V.ffc_spec_inv_(spec, cw.wt_x3(ctx, prec), cw.split_scale(prec), xs, cw.scale, cw.shift, tables, t1.v, u.v, flag,
@@ -1300,7 +1311,7 @@ def ffc_norm(ctx: Ctx, y: NHWC, u: NHWC, cw: ConvW, out: NHWC, gamma=None, beta=
     """out = act(IN([y_l | y_g + u conv2]) (1 + gamma) + beta) (+ res) (s2v_ffc_norm): SpectralTransform.conv2
     (ffc.py:164), FFC's out_xg sum (ffc.py:225-229) and ADAIN + LeakyReLU (base_blocks.py:143-157, :376-386)
     in one launch; ``pad_out`` also receives F.pad(out, 1, 'reflect')."""
-    prec = prec_code()
+    prec = layout_code(prec_code())
     xs, flag = _range(ctx, cw, u, prec)
     S2V.ffc_norm_(y.v, u.v, cw.wt_x3(ctx, prec), cw.split_scale(prec), xs, gamma, beta, eps, act, alpha,
                   None if res is None else res.v, out.v, None if pad_out is None else pad_out.v, flag, prec)

@@ -110,7 +110,7 @@ class LipSyncPipeline:
             raise ValueError(f"up_face_name {up_face_name!r} needs the GANimation model (up_face=)")
         self.up_face_name = up_face_name
         self._runner = None
-        self.reruns = 0             # replayed batches run again in bf16x3 after an f16x3 range overflow
+        self.reruns = 0             # replayed batches run again in bf16x3 after an f16x3 / f16 range overflow
 
     @torch.no_grad()
     def run_batch(self, mel: torch.Tensor, src: torch.Tensor, coeff: torch.Tensor, out_u8: torch.Tensor,
