@@ -405,7 +405,9 @@ int s2v_irfft2(const float *spec, int n, int h, int w, int c, int scs, const flo
  *   s2v_ffc_spec_inv: u = irfftn(relu(bn_fu(spec conv_fu))) + t1 -> u [n][h*h][cc] dense
  *   s2v_ffc_norm:     z = [y_l | y_g + u conv2] (y [n][h*h][C] with conv_to_l's and conv_l2g's outputs, pitch
  *                     ycs), out = act((z - mean) rstd (1 + gamma) + beta) (+ res); pad (optional, [n][h+2][h+2]
- *                     pitch pad_cs) also receives F.pad(out, 1, 'reflect').  out may be y itself.
+ *                     pitch pad_cs) also receives F.pad(out, 1, 'reflect').  out may be y itself.  act is
+ *                     S2V_ACT_NONE, S2V_ACT_RELU or S2V_ACT_LRELU (alpha); any other activation is refused
+ *                     (S2V_E_INVALID), not run as none.
  * w1 / wfu / w2: packed weights in the split layout of prec (s2v_split_weights with weight pre-scale
  * wt_scale; kpad >= the K of the conv, npad >= 128); scale / shift: folded BatchNorm per output channel (may
  * be NULL); x_scale: the f16x3 activation pre-scale of the conv's input (power of two, 1 = none); tables:

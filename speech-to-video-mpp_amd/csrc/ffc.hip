@@ -678,6 +678,12 @@ extern "C" int s2v_ffc_norm(const float *y, int ycs, int n, int h, const float *
                 (!pad || (pad_cs >= c && pad_cs % 4 == 0 && ((uintptr_t)pad % 16) == 0)) && ((uintptr_t)u % 16) == 0,
                 "ffc_norm: channel pitches / alignment");
     S2V_REQUIRE((gamma == nullptr) == (beta == nullptr) && (!gamma || gb_ns >= c), "ffc_norm: gamma / beta");
+    // the apply step is a slope on the negative side: no sigmoid / tanh / gelu_tanh
+    S2V_REQUIRE(act == S2V_ACT_NONE || act == S2V_ACT_RELU || act == S2V_ACT_LRELU,
+                "ffc_norm: activation %s is not implemented (none, relu and lrelu are)",
+                act == S2V_ACT_SIGMOID ? "sigmoid"
+                                       : (act == S2V_ACT_TANH ? "tanh"
+                                                              : (act == S2V_ACT_GELU_TANH ? "gelu_tanh" : "(unknown code)")));
     S2V_REQUIRE(w2_kpad >= cc && w2_kpad % 32 == 0 && pow2_or_one(wt_scale) && pow2_or_one(x_scale),
                 "ffc_norm: weights / scales");
     FfcArgs a = {};
