@@ -574,6 +574,27 @@ int s2v_l2norm_nhwc(const float *x, long long pixels, int c, long long x_cs, con
  * be >= the positions per image (sum of hs[l] ws[l]). */
 int s2v_s3fd_decode(const float *const *heads, const int *hs, const int *ws, int cs, int n, float thresh, float *cand,
                     int *count, int max_cand, s2v_stream_t stream);
+/* Batched exact greedy NMS (utils/nms/py_cpu_nms.py:10-37, detection/sfd/bbox.py:44-64) over the candidate
+ * buffers of s2v_s3fd_decode (row_stride 8) and s2v_retina_decode (row_stride 16, n = 1), where they lie.
+ * Row r of image b is at cand + (b * max_cand + r) * row_stride: [0] position index (int bits), [1..4] x1 y1
+ * x2 y2, [5] score, the rest payload; rows in any order; count[b] rows (device ints, clamped to max_cand).
+ *   1. rows with !(score > min_score) are dropped (-INFINITY: none but -inf scores);
+ *   2. the rest are ordered by score descending, among equal scores the larger position index first
+ *      (np.argsort(kind="stable")[::-1] on position-ordered rows; -0 equals +0);
+ *   3. top_k > 0: only the first top_k rows take part;
+ *   4. greedy sweep in fp32, unfused, in the reference's order: area = (x2-x1+1)*(y2-y1+1), inter =
+ *      max(0, xx2-xx1+1) * max(0, yy2-yy1+1), ovr = inter / (area_i + area_j - inter); row j survives kept
+ *      row i iff ovr <= iou_thresh (a NaN ovr suppresses);
+ *   5. kept[b] = the number of kept rows (uncapped); out + (b * keep_max + k) * row_stride gets the whole
+ *      k-th kept row, in keep order, for k < min(kept[b], keep_max); nothing else of out is written.
+ * status[b]: 0; 1 when steps 1 and 3 leave more than s2v_nms_capacity() rows (an image with more rows after
+ * step 1 is first cut to its top_k rows by key), 2 when a score of the image is NaN; then kept[b] = 0 and out
+ * is not written.
+ * row_stride 6..64, max_cand <= 2^24; cand, count, out, kept, status: device memory. */
+int s2v_nms(const float *cand, const int *count, int n, int max_cand, int row_stride, float iou_thresh,
+            float min_score, int top_k, int keep_max, float *out, int *kept, int *status, s2v_stream_t stream);
+/* rows per image s2v_nms can order (8192; RetinaFace's top_k is 5000) */
+int s2v_nms_capacity(void);
 /* cv2.warpAffine(src, M, (ow, oh), flags=INTER_LINEAR or INTER_AREA, BORDER_CONSTANT 0) on n HWC
  * images (dtype 0 uint8, 1 fp32, 2 fp64; pitches in elements): M = n device 2x3 fp64 forward
  * matrices, inverted on the device (invertAffineTransform); OpenCV's fixed-point source coordinates

@@ -148,6 +148,8 @@ _SIGS = {
     "s2v_u8_mean_nhwc4": (_c_int, [_vp, _c_int, _c_ll, _vp, _c_int, _vp, _vp]),
     "s2v_l2norm_nhwc": (_c_int, [_vp, _c_ll, _c_int, _c_ll, _vp, _c_float, _vp, _c_ll, _vp]),
     "s2v_s3fd_decode": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _vp, _c_int, _vp]),
+    "s2v_nms": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "s2v_nms_capacity": (_c_int, []),
     "s2v_bn_act_nhwc": (_c_int, [_vp, _c_ll, _c_int, _c_ll, _c_int, _vp, _vp, _vp, _c_ll, _c_int, _vp]),
     "s2v_fan_merge": (_c_int, [_vp, _c_ll, _vp, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_ll, _vp, _c_ll,
                                _vp, _vp, _vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp]),

@@ -19,6 +19,11 @@ tensors end to end).  On the device: the RetinaFace-R50 network and its prior de
 conversions, GPEN, RealESRNet, ParseNet, the paste-back composite and the final blends.  On the host,
 as in the reference: the NMS over the few thresholded candidates, the 5-point similarity fit
 (Umeyama, 5x2 points) and the per-face loop.  There is no CPU path.
+
+``nms="device"`` (opt-in; RetinaFaceDetection, restore.RetinaFaceDetector, face_detection.SFDDetector) runs the
+greedy NMS on the device as well (nms_device over s2v_nms) and copies only the kept rows.  Its order among
+equal scores is defined — the larger position (prior) index first — where the reference's
+``scores.argsort()[::-1]`` leaves it to NumPy's unstable sort; on distinct scores the two agree exactly.
 """
 from __future__ import annotations
 
@@ -38,6 +43,11 @@ FACE_MM = [0, 255, 255, 255, 255, 255, 255, 255, 0, 0, 255, 255, 255, 0, 0, 0, 0
 SMALL_FACE_KERNEL = ((0.0625, 0.125, 0.0625), (0.125, 0.25, 0.125), (0.0625, 0.125, 0.0625))   # :67-70
 
 WARP_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}
+
+NMS_MODES = ("host", "device")
+NMS_ENV = "S2V_NMS"
+# nms_device's per-image status: s2v_nms's 0 / 1 / 2, and 3 for more kept rows than keep_max
+NMS_OK, NMS_OVER_CAPACITY, NMS_NAN_SCORE, NMS_TRUNCATED = 0, 1, 2, 3
 
 
 def _ctx(device):
@@ -258,13 +268,59 @@ def filter2d_smooth(img: torch.Tensor) -> torch.Tensor:
     return y
 
 
+# ----------------------------------------------------------------------------- NMS on the device
+def nms_mode(nms="host") -> str:
+    """The ``nms=`` argument of the detectors: "host" (the default) or "device"; None reads S2V_NMS
+    (unset or empty: "host").  Anything else raises ValueError."""
+    source = "nms="
+    if nms is None:
+        nms, source = os.environ.get(NMS_ENV) or "host", NMS_ENV + "="
+    if nms not in NMS_MODES:
+        raise ValueError(f"{source}{nms!r}: {NMS_ENV} / nms= takes one of {', '.join(NMS_MODES)}")
+    return nms
+
+
+def nms_device(cand, count, n, max_cand, row_stride, iou_thresh, min_score=-math.inf, top_k=0, keep_max=1024):
+    """s2v_nms on the candidate buffer a decode kernel wrote.  ``cand``: device float32 tensor, row r of
+    image b at (b * max_cand + r) * row_stride: [position index bits, x1, y1, x2, y2, score, payload...], in
+    any order; ``count``: device tensor of n int32 row counts (or a float32 view of them).  Rows with
+    !(score > min_score) are dropped, the rest ordered by score descending (equal scores: the larger
+    position index first), the first ``top_k`` (> 0) swept greedily as py_cpu_nms does.  -> per image
+    (rows float32 [min(kept, keep_max), row_stride] in keep order, status): NMS_OK, NMS_OVER_CAPACITY (min_score
+    and top_k leave more than s2v_nms_capacity() rows), NMS_NAN_SCORE, or NMS_TRUNCATED (more than keep_max rows
+    were kept; rows holds the first keep_max).  One device -> host copy of [kept | status | out]."""
+    n, max_cand, rs, keep_max = int(n), int(max_cand), int(row_stride), int(keep_max)
+    if cand.numel() < n * max_cand * rs or count.numel() < n:
+        raise ValueError(f"nms_device: cand / count hold {cand.numel()} / {count.numel()} elements, "
+                         f"{n} images of {max_cand} rows of {rs} floats need {n * max_cand * rs} / {n}")
+    buf = torch.empty(n * (2 + keep_max * rs), device=cand.device)
+    ctx = _ctx(cand.device)
+    base = buf.data_ptr()
+    check(ctx.lib.s2v_nms(cand.data_ptr(), count.data_ptr(), n, max_cand, rs, float(iou_thresh), float(min_score),
+                          int(top_k), keep_max, base + 8 * n, base, base + 4 * n, ctx.stream), "s2v_nms")
+    host = buf.cpu().numpy()
+    kept, status = host[:n].view(np.int32), host[n: 2 * n].view(np.int32)
+    out = host[2 * n:].reshape(n, keep_max, rs)
+    res = []
+    for i in range(n):
+        st = int(status[i])
+        if st == NMS_OK and kept[i] > keep_max:
+            st = NMS_TRUNCATED
+        res.append((out[i, : min(int(kept[i]), keep_max)].copy() if st in (NMS_OK, NMS_TRUNCATED)
+                    else np.zeros((0, rs), np.float32), st))
+    return res
+
+
 # ----------------------------------------------------------------------------- detection
 class RetinaFaceDetection:
     """retinaface_detection.py:19-124 on the device.  ``net``: an s2v_amd.models.RetinaFace; without
-    it the weights load from base_dir/weights/<network>.pth."""
+    it the weights load from base_dir/weights/<network>.pth.  ``nms``: "host" (py_cpu_nms, the default),
+    "device" (nms_device; ``detect`` with resize != 1 stays on the host, where the boxes are rescaled before
+    the NMS) or None for S2V_NMS."""
 
-    def __init__(self, base_dir="./", device="cuda", network="RetinaFace-R50", net=None):
+    def __init__(self, base_dir="./", device="cuda", network="RetinaFace-R50", net=None, nms="host"):
         from . import models
+        self.nms = nms_mode(nms)
         self.device = torch.device(device)
         self.cfg = dict(models.retinaface_arch.CFG_RE50)
         self.pretrained_path = os.path.join(base_dir, "weights", network + ".pth")
@@ -280,6 +336,27 @@ class RetinaFaceDetection:
                                          x4.ptr, ctx.stream), "s2v_bgr_mean_nhwc4")
         maps, _ = self.net.head_maps(x4)
         return maps
+
+    def decode(self, maps, im_h, im_w, confidence_threshold):
+        """s2v_retina_decode -> (cand float32, count int32 [1], max_cand = the rows cand holds, >= the priors)
+        on the device: the rows of the priors whose score > threshold, in slot order (nms_device's input)."""
+        P = sum(2 * m.h * m.w for m in maps)
+        if self._cand is None or self._cand[0].numel() < P * 16:
+            self._cand = (torch.empty(P * 16, device=self.device), torch.empty(1, dtype=torch.int32, device=self.device))
+        cand, count = self._cand
+        ctx = _ctx(self.device)
+        heads = (ctypes.c_void_p * 3)(*[m.ptr for m in maps])
+        hs = (ctypes.c_int * 3)(*[m.h for m in maps])
+        ws = (ctypes.c_int * 3)(*[m.w for m in maps])
+        check(ctx.lib.s2v_retina_decode(heads, hs, ws, maps[0].cs, im_h, im_w, float(confidence_threshold),
+                                        cand.data_ptr(), count.data_ptr(), cand.numel() // 16, ctx.stream),
+              "s2v_retina_decode")
+        return cand, count, cand.numel() // 16
+
+    def kept_rows(self, maps, im_h, im_w, confidence_threshold, nms_threshold, top_k, keep_max):
+        """decode + nms_device -> (rows [K,16] in keep order, status) of the one image."""
+        cand, count, max_cand = self.decode(maps, im_h, im_w, confidence_threshold)
+        return nms_device(cand, count, 1, max_cand, 16, nms_threshold, top_k=top_k, keep_max=keep_max)[0]
 
     def candidates(self, maps, im_h, im_w, confidence_threshold):
         """Priors whose score > threshold, as the reference's thresholded arrays in prior order:
@@ -312,6 +389,13 @@ class RetinaFaceDetection:
             img = post.resize_linear(img.float(), (ow, oh), fxfy=(ss, ss))
             im_height, im_width = oh, ow
         maps = self.head_maps(img)
+        if self.nms == "device" and resize == 1 and top_k > 0 and keep_top_k > 0:
+            # the first keep_top_k kept rows are what the host path keeps: NMS_TRUNCATED is no failure here
+            rows, status = self.kept_rows(maps, im_height, im_width, confidence_threshold, nms_threshold, top_k,
+                                          keep_top_k)
+            if status in (NMS_OK, NMS_TRUNCATED):
+                landms = rows[:, 6:16].reshape((-1, 5, 2)).transpose((0, 2, 1)).reshape(-1, 10)
+                return rows[:, 1:6] / ss, landms / ss
         boxes, scores, landms = self.candidates(maps, im_height, im_width, confidence_threshold)
         if resize != 1:
             boxes, landms = boxes / resize, landms / resize

@@ -14,7 +14,10 @@ On the device: the channel flip + mean subtraction of a batch of uint8 frames (s
 the S3FD network (models.S3FD: VGG-16 convs, max pools, s2v_l2norm_nhwc, fused heads) and
 batch_detect's softmax + 0.05 threshold + prior decode over all six levels of the whole batch
 (s2v_s3fd_decode).  One device -> host copy per batch brings the per-image counts and candidate rows;
-the NMS over those few rows and the box arithmetic stay on the host, as in the reference.
+the NMS over those few rows and the box arithmetic stay on the host, as in the reference.  With
+SFDDetector(nms="device") (opt-in) the NMS runs on the device too (face.nms_device over s2v_nms, with score >
+0.5 as its pre-filter) and the copy brings only the kept rows; among equal scores it takes the larger position
+index first, where the reference leaves the order to NumPy's unstable sort.
 
 The 68 landmarks of a face (face_alignment's get_landmarks_from_image / get_landmarks_from_batch, which
 third_part/face3d/extract_kp_videos.py:15-57 calls) run on the device as well: utils.crop of every detected
@@ -44,7 +47,7 @@ import torch
 
 from . import post
 from ._lib import check
-from .face import py_cpu_nms
+from .face import NMS_OK, nms_device, nms_mode, py_cpu_nms
 from .ops import NHWC
 
 MEANS = (104.0, 117.0, 123.0)           # detect.py:59, applied to the channels as the detector gets them
@@ -79,10 +82,14 @@ def nms_keep(rows: np.ndarray):
 
 class SFDDetector:
     """sfd_detector.py:16-59 on the device.  ``net``: an s2v_amd.models.S3FD; without it the weights
-    load from ``path_to_detector`` (strict).  Nothing is ever downloaded: a missing file is an error."""
+    load from ``path_to_detector`` (strict).  Nothing is ever downloaded: a missing file is an error.
+    ``nms``: "host" (nms_keep, the default), "device" (nms_device; an image with more than ``keep_max`` kept
+    boxes, or one the kernel refuses, takes the host path alone) or None for S2V_NMS."""
 
-    def __init__(self, device, path_to_detector=None, net=None, verbose=False):
+    def __init__(self, device, path_to_detector=None, net=None, verbose=False, nms="host", keep_max=1024):
         from . import models
+        self.nms = nms_mode(nms)
+        self.keep_max = int(keep_max)
         self.device = torch.device(device)
         self.verbose = verbose
         if net is None:
@@ -135,7 +142,42 @@ class SFDDetector:
     def detect_from_batch(self, images, flip=False):
         """-> per image, the list of kept [x1, y1, x2, y2, score] float32 rows (sfd_detector.py:41-47).
         ``flip``: reverse the channel order on the device first (FaceAlignment's images[..., ::-1])."""
-        return [nms_keep(r[:, 1:6]) for r in self.candidates(self.head_maps(images, flip))]
+        maps = self.head_maps(images, flip)
+        if self.nms == "device":
+            return self.detect_device(maps)
+        return [nms_keep(r[:, 1:6]) for r in self.candidates(maps)]
+
+    def decode(self, maps):
+        """s2v_s3fd_decode -> (cand float32 [n * P * 8], count [n] int32 bits, n, P) on the device: the rows
+        of the positions whose score > 0.05, in slot order (nms_device's input)."""
+        n = maps[0].n
+        P = sum(m.h * m.w for m in maps)
+        if self._cand is None or self._cand.numel() < n * (P * 8 + 1):
+            self._cand = torch.empty(n * (P * 8 + 1), device=self.device)
+        buf = self._cand[: n * (P * 8 + 1)]
+        count, cand = buf[:n], buf[n:]
+        ctx = post._ctx(self.device)
+        heads = (ctypes.c_void_p * 6)(*[m.ptr for m in maps])
+        hs = (ctypes.c_int * 6)(*[m.h for m in maps])
+        ws = (ctypes.c_int * 6)(*[m.w for m in maps])
+        check(ctx.lib.s2v_s3fd_decode(heads, hs, ws, maps[0].cs, n, SCORE_THRESH, cand.data_ptr(), count.data_ptr(),
+                                      P, ctx.stream), "s2v_s3fd_decode")
+        return cand, count, n, P
+
+    def detect_device(self, maps):
+        """detect_from_batch's lists with the NMS on the device: nms(0.3) over the rows with score > 0.5 (a
+        row at or below 0.5 comes after every row above it, suppresses none of them and is dropped after the
+        NMS anyway).  One device -> host copy of the kept rows."""
+        cand, count, n, P = self.decode(maps)
+        res = nms_device(cand, count, n, P, 8, NMS_THRESH, min_score=KEEP_THRESH, keep_max=self.keep_max)
+        host, out = None, []
+        for i, (rows, status) in enumerate(res):
+            if status != NMS_OK:
+                host = self.candidates(maps) if host is None else host
+                out.append(nms_keep(host[i][:, 1:6]))
+            else:
+                out.append(list(rows[:, 1:6]))
+        return out
 
     def detect_from_image(self, img):
         """sfd_detector.py:31-39 for an image array / tensor [H,W,3]."""

@@ -258,13 +258,13 @@ def _semantic(frames_bgr: torch.Tensor, ckpt_dir, dev, lms=None):
     return ext.face_3dmm_extraction(rgb, lms), kind
 
 
-def _landmarks(frames_bgr: torch.Tensor, ckpt_dir, dev, detector=None):
+def _landmarks(frames_bgr: torch.Tensor, ckpt_dir, dev, detector=None, nms="host"):
     """facing.py:89-97: KeypointExtractor().extract_keypoint on the RGB frames -> (landmarks [n, 68, 2],
     FAN weight kind, frames without a face).  FAN weights from <checkpoints>/2DFAN4.pth, or the synthetic
     FAN_SYNTH preset without it; the boxes come from the S3FD detector of _face_detector."""
     from . import face3d
     if detector is None:
-        detector, kind = _landmark_detector(ckpt_dir, dev)
+        detector, kind = _landmark_detector(ckpt_dir, dev, nms)
     else:
         kind = "given detector"
     kp = face3d.KeypointExtractor(detector)
@@ -272,7 +272,7 @@ def _landmarks(frames_bgr: torch.Tensor, ckpt_dir, dev, detector=None):
     return lms.astype(np.float32), kind, kp.misses
 
 
-def _landmark_detector(ckpt_dir, dev):
+def _landmark_detector(ckpt_dir, dev, nms="host"):
     """KeypointExtractor's detector: FaceAlignment over S3FD (_face_detector) with the FAN weights of
     <checkpoints>/2DFAN4.pth, or the synthetic FAN_SYNTH preset without it -> (detector, FAN weight kind)."""
     from . import models, synth
@@ -284,7 +284,7 @@ def _landmark_detector(ckpt_dir, dev):
         fan = models.FAN()
         fan.load_state_dict(synth.synth_torch_state_dict(FANParams(), **synth.FAN_SYNTH), strict=True)
         fan, kind = fan.eval(), "2DFAN4 synthetic"
-    detector, _ = _face_detector(ckpt_dir, dev)
+    detector, _ = _face_detector(ckpt_dir, dev, nms)
     detector.face_alignment_net = fan
     return detector, kind
 
@@ -315,9 +315,10 @@ class BoxedStitch:
         return out.permute(0, 3, 1, 2).contiguous()
 
 
-def _face_detector(ckpt_dir, dev):
+def _face_detector(ckpt_dir, dev, nms="host"):
     """face_detect's default detector (inference_utils.py:111-113): FaceAlignment(_2D) over S3FD with the
-    weights of <checkpoints>/s3fd.pth, or the synthetic preset without it -> (detector, weight kind)."""
+    weights of <checkpoints>/s3fd.pth, or the synthetic preset without it -> (detector, weight kind).
+    ``nms``: SFDDetector's ("host" / "device")."""
     from . import face_detection, models, synth
     from .models.s3fd_arch import S3FDParams
     path = os.path.join(ckpt_dir or "", "s3fd.pth")
@@ -327,7 +328,7 @@ def _face_detector(ckpt_dir, dev):
         net = models.S3FD()
         net.load_state_dict(synth.s3fd_state_dict(S3FDParams()), strict=True)
         net, kind = net.eval(), "s3fd synthetic"
-    sfd = face_detection.SFDDetector(dev, net=net)
+    sfd = face_detection.SFDDetector(dev, net=net, nms=nms)
     return face_detection.FaceAlignment(face_detection.LandmarksType._2D, device=dev, flip_input=False,
                                         detector=sfd), kind
 
@@ -346,12 +347,14 @@ def _up_face_model(ckpt_dir, dev):
     return ganimation.GANimationModel().initialize(net_gen=net, device=dev).setup(), kind
 
 
-def _ref_enhancer(ckpt_dir, dev):
+def _ref_enhancer(ckpt_dir, dev, nms="host"):
     """inference.py:224-226: FaceEnhancement(in_size=512, channel_multiplier=2, narrow=1, sr_scale=4,
     model='GPEN-BFR-512', use_sr=False) as a hook on the stabilised uint8 RGB references."""
     from . import face as faces
-    enh = faces.FaceEnhancement(base_dir=ckpt_dir or "checkpoints", in_size=512, channel_multiplier=2, narrow=1,
-                                sr_scale=4, model="GPEN-BFR-512", use_sr=False, device=dev)
+    base = ckpt_dir or "checkpoints"
+    enh = faces.FaceEnhancement(base_dir=base, in_size=512, channel_multiplier=2, narrow=1, sr_scale=4,
+                                model="GPEN-BFR-512", use_sr=False, device=dev,
+                                facedetector=faces.RetinaFaceDetection(base, dev, nms=nms))
     return reference_hook(enh)
 
 
@@ -373,7 +376,8 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         ref_hook=None, restore: bool = True, restorer=None, enhancer=None, face_det: bool = False,
         pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None,
         landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None,
-        up_face: str = "original", without_rl1: bool = False, up_face_model=None, precision: str | None = None):
+        up_face: str = "original", without_rl1: bool = False, up_face_model=None, precision: str | None = None,
+        nms: str | None = "host"):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -398,9 +402,14 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     over ``ckpt_dir``/30_net_gen.pth or the synthetic preset); ``meta`` gains ``up_face``, ``without_rl1`` and
     ``up_face_weights``.  ``precision``: the conv arithmetic of the whole clip (an ops.set_precision name; None
     leaves ops.PRECISION alone), restored afterwards; ``meta["conv_arith"]`` names the arithmetic that ran.  The
-    opt-in "f16" (single-pass f16 products) is outside the fp32 parity bar: about 0.5 grey level on average."""
+    opt-in "f16" (single-pass f16 products) is outside the fp32 parity bar: about 0.5 grey level on average.
+    ``nms``: where the greedy NMS of every detector this call builds runs (S3FD, and RetinaFace in
+    FaceEnhancement and GFPGANer): "host" (the default), "device" (face.nms_device; equal scores take the larger
+    position index first) or None for S2V_NMS; given detectors keep their own.  ``meta["nms"]`` records it."""
     kw = dict(locals())                                     # the arguments (nothing else is bound yet)
     from . import audio, ops, pipeline, post, synth
+    from . import face as faces
+    nms = kw["nms"] = faces.nms_mode(nms)                   # ValueError on a bad name before anything runs
     if precision is not None:
         kw["precision"] = None
         with ops.precision(precision):                      # ValueError on a bad name before anything runs
@@ -424,7 +433,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     if face_det:
         from . import face_detection
         if detector is None:
-            detector, box_source = _face_detector(ckpt_dir, dev)
+            detector, box_source = _face_detector(ckpt_dir, dev, nms)
         else:
             box_source = "given detector"
         det = face_detection.face_detect(frames, pads=pads, nosmooth=nosmooth, jaw_correction=True,
@@ -443,19 +452,19 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     check(ctx.lib.s2v_u8_to_gan(crops.data_ptr(), n, 256, 256, src.data_ptr(), ctx.stream), "s2v_u8_to_gan")
     lms = None
     if landmarks:
-        lms, lkind, lmiss = _landmarks(frames, ckpt_dir, dev, landmark_detector)   # facing.py:89-97
+        lms, lkind, lmiss = _landmarks(frames, ckpt_dir, dev, landmark_detector, nms)   # facing.py:89-97
         lms, lrej = _usable_landmarks(lms, H, W, _lm3d(ckpt_dir))
     semantic, skind = _semantic(frames, ckpt_dir, dev, lms)                        # facing.py:100-130
     expression = synth.hash_array("inference.expression", (64,), -1.0, 1.0)        # expression.mat is absent
     coeffs = torch.from_numpy(pipeline.dnet_coefficients(semantic, expression, False, 0, n)).to(dev)
     if ref_enhance and ref_hook is None:
-        ref_hook = _ref_enhancer(ckpt_dir, dev)
+        ref_hook = _ref_enhancer(ckpt_dir, dev, nms)
     stitcher = None
     if stitch:
         from . import face3d
         from . import stitch as stitching
         if stitch_detector is None:
-            stitch_detector, stkind = _landmark_detector(ckpt_dir, dev)
+            stitch_detector, stkind = _landmark_detector(ckpt_dir, dev, nms)
         else:
             stkind = "given detector"
         stitcher = BoxedStitch(stitching.Stitcher(face3d.KeypointExtractor(stitch_detector), image_size=256), boxes)
@@ -482,15 +491,16 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         post.resize_linear(hwc[i], (bx2 - bx1, by2 - by1), out=out[i, by1:by2, bx1:bx2])
     enhanced = None
     if enhance:
-        from . import face as faces
         base = ckpt_dir or "checkpoints"
         enh = enhancer or faces.FaceEnhancement(base_dir=base, in_size=2048, channel_multiplier=2, narrow=1,
                                                 sr_scale=2, sr_model=None, model="GPEN-BFR-2048", use_sr=True,
-                                                device=device)                       # inference.py:228-231
+                                                device=device,                       # inference.py:228-231
+                                                facedetector=faces.RetinaFaceDetection(base, device, nms=nms))
         if restore and restorer is None:
-            from .restore import GFPGANer
+            from .restore import GFPGANer, RetinaFaceDetector
             restorer = GFPGANer(model_path=os.path.join(base, "GFPGANv1.4.pth"), upscale=1, arch="clean",
-                                channel_multiplier=2, bg_upsampler=None, device=device, base_dir=base)   # :255-256
+                                channel_multiplier=2, bg_upsampler=None, device=device, base_dir=base,
+                                face_det=RetinaFaceDetector(base, device, nms=nms))   # :255-256
         mouth = post.MouthBlend(enh.faceparser)
         enhanced = []
         for i in range(n):
@@ -507,7 +517,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
             "mel_cols": int(mel.shape[1]), "mel_windows": int(chunks.shape[0]), "wav_samples_16k": int(len(wav)),
             "box": [y1, y2, x1, x2], "semantic": skind, "ref_enhance": ref_hook is not None,
             "restore": bool(enhance and restore), "up_face": up_face, "without_rl1": bool(without_rl1),
-            "up_face_weights": ukind, "conv_arith": ops.PRECISION,
+            "up_face_weights": ukind, "conv_arith": ops.PRECISION, "nms": nms,
             "seconds": round(time.time() - t0, 3)}
     if face_det:
         meta["boxes"] = [list(b) for b in boxes]
@@ -558,6 +568,9 @@ def build_parser():
                     help="conv arithmetic of the whole clip (default: the process setting, S2V_PRECISION or f16x3); "
                          "f16 is the fast single-pass mode, OUTSIDE the fp32 parity bar (about 0.5 grey level on "
                          "average, 3-5 at the worst pixel)")
+    ap.add_argument("--nms", default=None, choices=["host", "device"],
+                    help="where every detector's greedy NMS runs (default: S2V_NMS, else host); device: the "
+                         "batched kernel, equal scores take the larger position index first")
     return ap
 
 
@@ -568,7 +581,8 @@ def main(argv=None):
     r = run(a.face, a.audio, a.max_frames, a.LNet_batch_size, a.box_frac, a.checkpoints, a.enhance,
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
             nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
-            stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1, precision=a.precision)
+            stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1, precision=a.precision,
+            nms=a.nms)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     arrays = {"frames": r["frames"].cpu().numpy(), "preds": r["preds"].cpu().numpy()}
     if r["enhanced"] is not None:

@@ -51,10 +51,14 @@ CONF_THRESHOLD = 0.97                      # get_face_landmarks_5: detect_faces(
 # ----------------------------------------------------------------------------- detection
 class RetinaFaceDetector:
     """facexlib detection/retinaface.py RetinaFace.detect_faces (use_origin_size=True: no resize) on
-    the device network of face.RetinaFaceDetection (same R50 architecture, BGR means 104/117/123)."""
+    the device network of face.RetinaFaceDetection (same R50 architecture, BGR means 104/117/123).
+    ``nms``: "host" (py_cpu_nms, the default), "device" (face.nms_device, at most ``keep_max`` faces; an image
+    with more, or one the kernel refuses, takes the host path) or None for S2V_NMS."""
 
-    def __init__(self, base_dir="./", device="cuda", network="RetinaFace-R50", net=None):
-        self.det = faces.RetinaFaceDetection(base_dir, device, network, net)
+    def __init__(self, base_dir="./", device="cuda", network="RetinaFace-R50", net=None, nms="host", keep_max=750):
+        self.det = faces.RetinaFaceDetection(base_dir, device, network, net, nms=nms)
+        self.nms = self.det.nms
+        self.keep_max = int(keep_max)
         self.device = self.det.device
 
     def detect_faces(self, image, conf_threshold=0.8, nms_threshold=0.4, use_origin_size=True):
@@ -64,6 +68,10 @@ class RetinaFaceDetector:
         img = faces._frame(image, self.device)
         h, w = img.shape[:2]
         maps = self.det.head_maps(img)
+        if self.nms == "device":
+            rows, status = self.det.kept_rows(maps, h, w, conf_threshold, nms_threshold, 0, self.keep_max)
+            if status == faces.NMS_OK:
+                return rows[:, 1:16].copy()
         boxes, scores, landms = self.det.candidates(maps, h, w, conf_threshold)
         order = scores.argsort()[::-1]
         boxes, landms, scores = boxes[order], landms[order], scores[order]

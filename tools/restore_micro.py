@@ -4,7 +4,7 @@ frame with synthetic weights: the RetinaFace-R50 network and detect_faces(img, 0
 (random weights: the candidate count, hence the host NMS, is not a real frame's), then the composition with a fixed centre face (LMEDS fit,
 gray-border warp, GFPGANv1Clean, tensor2img, paste-back).  ms per call, best of --iters.
 
-    python tools/restore_micro.py [--h 720 --w 1280] [--iters 10]"""
+    python tools/restore_micro.py [--h 720 --w 1280] [--iters 10] [--nms host|device]"""
 import argparse
 import os
 import sys
@@ -45,6 +45,7 @@ def main():
     ap.add_argument("--w", type=int, default=1280)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--no-detect", action="store_true", help="skip the RetinaFace timing (profiling runs)")
+    ap.add_argument("--nms", default="host", choices=["host", "device"], help="where detect_faces runs its NMS")
     a = ap.parse_args()
     from helpers import GFPGAN_KW, synth_sd
     from oracle import restore as OR
@@ -54,7 +55,7 @@ def main():
     img = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (H, W, 3), dtype=np.uint8)).to(dev)
     rf = models.RetinaFace()
     rf.load_state_dict(synth_sd("retinaface"), strict=True)
-    det = restore.RetinaFaceDetector(device=dev, net=rf.eval())
+    det = restore.RetinaFaceDetector(device=dev, net=rf.eval(), nms=a.nms)
     g = models.GFPGANv1Clean(**GFPGAN_KW)
     g.load_state_dict(synth_sd("gfpgan"), strict=True)
     sc = min(H, W) * 0.5 / 512
@@ -67,7 +68,7 @@ def main():
     if not a.no_detect:
         res["RetinaFace-R50 network (head maps)"] = best_ms(lambda: det.det.head_maps(img), a.iters)
         k = len(det.detect_faces(img, 0.97))
-        res[f"detect_faces(img, 0.97) ({k} faces kept)"] = best_ms(lambda: det.detect_faces(img, 0.97), a.iters)
+        res[f"detect_faces(img, 0.97) ({k} faces kept, nms {a.nms})"] = best_ms(lambda: det.detect_faces(img, 0.97), a.iters)
 
     def align():
         fh.clean_all()
