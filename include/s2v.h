@@ -595,6 +595,38 @@ int s2v_nms(const float *cand, const int *count, int n, int max_cand, int row_st
             float min_score, int top_k, int keep_max, float *out, int *kept, int *status, s2v_stream_t stream);
 /* rows per image s2v_nms can order (8192; RetinaFace's top_k is 5000) */
 int s2v_nms_capacity(void);
+/* Baseline JPEG (ITU T.81, JFIF) of n uint8 HWC frames, one complete file per frame, all in integer
+ * arithmetic: the bytes are reproducible.  frames: pixel (y, x) of frame b at frames + b * frame_stride_bytes +
+ * y * pitch_bytes + 3 x, channels R G B (bgr 0) or B G R (bgr 1).  The stream:
+ *   header   copied from ``header`` (header_bytes): SOI, APP0 JFIF 1.1 (units 0, density 1x1), DQT 0 (luma),
+ *            DQT 1 (chroma), SOF0 (8 bit, true h and w, component 1 sampling 0x22 table 0, components 2 and 3
+ *            sampling 0x11 table 1), DHT DC0, AC0, DC1, AC1 (the Annex K.3 typical tables, which the kernels
+ *            code with), DRI (interval = MCUs per MCU row), SOS ((1, 0x00), (2, 0x11), (3, 0x11); 0, 63, 0);
+ *   pixels   the frame is padded to multiples of 16 by edge replication; with >> an arithmetic shift,
+ *            Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16,
+ *            Cb = (-11059 R - 21709 G + 32768 B + 32768 + (128 << 16)) >> 16,
+ *            Cr = ( 32768 R - 27439 G -  5329 B + 32768 + (128 << 16)) >> 16, each clamped to 0..255;
+ *            chroma is the 2x2 sum (a + b + c + d + 2) >> 2; level shift -128;
+ *   FDCT     CI[u][x] = rint(8192 k(u) cos((2x + 1) u pi / 16)), k(0) = sqrt(1/8), k(u > 0) = 1/2;
+ *            T = (CI X + 1024) >> 11, F = (T CI^T + 16384) >> 15;
+ *   quantise sign(F) ((|F| + (t >> 1)) / t) with t = qtables[0][z] (luma) or qtables[1][z] (chroma), z the
+ *            zigzag position (the order of a DQT segment); then DC clamped to [-1024, 1023], AC to +-1023;
+ *   entropy  T.81 F.1.2, one interleaved scan, MCU = Y00 Y01 Y10 Y11 Cb Cr; one restart interval per MCU row
+ *            (DC predictors reset), its last byte padded with 1-bits, every 0xFF data byte followed by 0x00,
+ *            RSTm with m = row & 7 between rows, none after the last; then EOI.
+ * Frame b's file starts at out + b * capacity.  sizes[b]: its byte count, reported even when it does not fit;
+ * status[b]: 0, or 1 when sizes[b] > capacity: then nothing of that slot is written.  No byte outside the slots
+ * is written.  Stream-ordered, no host synchronisation.  h, w <= 65535; pitch_bytes >= 3 w;
+ * ws >= s2v_jpeg_ws_bytes(n, h, w) bytes, 16-byte aligned (int16 coefficients [n][mcu][6][64], the interval
+ * sizes, and a worst-case staging area per interval); frames, header, qtables, out, sizes, status, ws: device
+ * memory. */
+int s2v_jpeg_encode(const uint8_t *frames, int n, int h, int w, long pitch_bytes, long frame_stride_bytes, int bgr,
+                    const uint8_t *header, int header_bytes, const uint16_t *qtables, uint8_t *out, long capacity,
+                    int *sizes, int *status, void *ws, long ws_bytes, s2v_stream_t stream);
+long s2v_jpeg_ws_bytes(int n, int h, int w);
+/* a bound no frame's file can exceed, the header excluded: 416 bytes per 8x8 block (1658 bits of codes at the
+ * most, every byte stuffed) and the marker after each MCU row */
+long s2v_jpeg_worst_bytes(int h, int w);
 /* cv2.warpAffine(src, M, (ow, oh), flags=INTER_LINEAR or INTER_AREA, BORDER_CONSTANT 0) on n HWC
  * images (dtype 0 uint8, 1 fp32, 2 fp64; pitches in elements): M = n device 2x3 fp64 forward
  * matrices, inverted on the device (invertAffineTransform); OpenCV's fixed-point source coordinates

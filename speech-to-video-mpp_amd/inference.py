@@ -44,6 +44,10 @@ Steps (reference file:line in brackets):
   * --enhance: FaceEnhancement (SR x2, RetinaFace, GPEN-2048, parse-mask paste) on each pasted frame
     against the 2x frame [inference.py:228-231, :317-328]; needs real checkpoints (synthetic
     RetinaFace weights detect no faces, and the reference raises on a frame without one).
+  * --outfile NAME.avi: the frames (the --enhance output when there is one) as a Motion-JPEG AVI with the
+    audio of --audio, the counterpart of cv2.VideoWriter + the ffmpeg mux [inference.py:246-249, :325-336]:
+    baseline JPEG on the device at --jpeg_quality (s2v_amd.mjpeg, in batches of --LNet_batch_size), PCM at
+    the file's own rate and channel count cut to the clip.  Any other extension: the arrays as an .npz.
 Weights come from --checkpoints (LNet.pth / ENet.pth / DNet.pt as models.load_network /
 load_DNet read them) or, when absent, from the portable synthetic generator (s2v_amd.synth).
 """
@@ -539,7 +543,9 @@ def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--face", required=True, help="MP4 (header read; synthetic frames) or uint8 [N,H,W,3] .npy")
     ap.add_argument("--audio", required=True, help="PCM .wav")
-    ap.add_argument("--outfile", default="results/inference_frames.npz")
+    ap.add_argument("--outfile", default="results/inference_frames.npz",
+                    help="NAME.avi: a Motion-JPEG AVI of the frames (the --enhance output when there is one) with the "
+                         "audio of --audio; anything else: the uint8 arrays as a compressed .npz")
     ap.add_argument("--max_frames", type=int, default=8)
     ap.add_argument("--LNet_batch_size", type=int, default=16)
     ap.add_argument("--box_frac", type=float, default=0.6)
@@ -571,19 +577,42 @@ def build_parser():
     ap.add_argument("--nms", default=None, choices=["host", "device"],
                     help="where every detector's greedy NMS runs (default: S2V_NMS, else host); device: the "
                          "batched kernel, equal scores take the larger position index first")
+    ap.add_argument("--jpeg_quality", type=int, default=95,
+                    help="with --outfile NAME.avi: JPEG quality 1..100 (the reference asks ffmpeg for its best, -q:v 1)")
     return ap
+
+
+def write_avi(path: str, frames: torch.Tensor, fps: float, audio_path: str, quality: int = 95, batch: int = 16) -> int:
+    """The reference's cv2.VideoWriter + ffmpeg mux (inference.py:246-249, :325-336) as one Motion-JPEG AVI:
+    uint8 BGR [n, H, W, 3] device frames through mjpeg.JpegEncoder in batches of ``batch``, with the PCM of
+    ``audio_path`` at its own rate and channel count, cut to the clip.  -> the file's size in bytes."""
+    from . import mjpeg
+    n, H, W = frames.shape[:3]
+    enc = mjpeg.JpegEncoder(H, W, quality=quality, order="bgr", device=frames.device)
+    with mjpeg.AviWriter(path, W, H, fps, audio=mjpeg.wav_pcm16(audio_path)) as avi:
+        for s in range(0, n, max(1, batch)):
+            for data in enc.encode_to_host(frames[s:s + max(1, batch)]):
+                avi.write(data)
+    return os.path.getsize(path)
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     if len(a.pads) != 4:
         raise SystemExit("--pads takes four integers: top bottom left right")
+    if a.outfile.lower().endswith(".avi") and not 1 <= a.jpeg_quality <= 100:
+        raise SystemExit("--jpeg_quality takes 1 to 100")
     r = run(a.face, a.audio, a.max_frames, a.LNet_batch_size, a.box_frac, a.checkpoints, a.enhance,
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
             nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
             stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1, precision=a.precision,
             nms=a.nms)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
+    if a.outfile.lower().endswith(".avi"):
+        video = r["enhanced"] if r["enhanced"] is not None else r["frames"]
+        size = write_avi(a.outfile, video, r["meta"]["fps"], a.audio, a.jpeg_quality, a.LNet_batch_size)
+        print(json.dumps(dict(r["meta"], outfile=a.outfile, video_bytes=size, jpeg_quality=a.jpeg_quality)))
+        return 0
     arrays = {"frames": r["frames"].cpu().numpy(), "preds": r["preds"].cpu().numpy()}
     if r["enhanced"] is not None:
         arrays["enhanced"] = r["enhanced"].cpu().numpy()
