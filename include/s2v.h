@@ -627,6 +627,49 @@ long s2v_jpeg_ws_bytes(int n, int h, int w);
 /* a bound no frame's file can exceed, the header excluded: 416 bytes per 8x8 block (1658 bits of codes at the
  * most, every byte stuffed) and the marker after each MCU row */
 long s2v_jpeg_worst_bytes(int h, int w);
+/* Baseline JPEG decode (ITU T.81: SOF0, 8 bit, Y Cb Cr in one interleaved scan) of n streams into uint8 HWC
+ * frames, all in integer arithmetic: the pixels equal libjpeg's default decoder (JDCT_ISLOW, fancy upsampling,
+ * which is what Pillow decodes with) bit for bit.  All frames of a call share h, w and sampling: 0 = 4:4:4,
+ * 1 = 4:2:2 (luma 2x1), 2 = 4:2:0 (luma 2x2), chroma 1x1; an MCU is 3, 4 or 6 blocks, luma first.  The host parses
+ * the headers (s2v_amd.mjpeg.parse_jpeg) and hands over:
+ *   data       data_bytes bytes that hold the entropy-coded segments (the whole files, concatenated);
+ *   intervals  int32 [n_intervals][5]: (byte offset in data, byte length, frame, first MCU, MCU count) of every
+ *              restart interval of every frame, the RSTm markers excluded; frame b's rows are
+ *              frame_first[b] .. frame_first[b + 1] - 1 (int32 [n + 1]), max_per_frame the largest such count.  A
+ *              stream without restart markers is one interval: correct, and decoded by a single lane;
+ *   qtables    uint16 [n][3][64], component c of frame b, in zigzag order (a DQT segment's order);
+ *   huff_sets  uint8 [n_sets][6][272]: the (DC, AC) tables of components 0, 1, 2, each BITS[16] then
+ *              HUFFVAL[256] as a DHT segment gives them; frame b decodes with set set_index[b] (int32 [n]), so
+ *              equal sets are uploaded once.
+ * The arithmetic, with >> an arithmetic shift:
+ *   entropy    T.81 F.2.2 per interval: 0xFF 0x00 is one data byte 0xFF, the DC predictors start at 0, int16
+ *              coefficients; no byte at or past the interval's end is read;
+ *   dequantise coef[z] * q[z], placed at the natural index of zigzag position z;
+ *   IDCT       jidctint's jpeg_idct_islow in 64-bit integers (constants at 13 bits): columns (x + 1024) >> 11, rows
+ *              (x + (1 << 17)) >> 18, then + 128 and a plain clamp to 0..255.  libjpeg clamps through a masked table
+ *              that wraps beyond +-512 around the centre: equality with it is claimed inside that range only;
+ *   upsample   over the real chroma size ch = ceil(h / v), cw = ceil(w / hs), edges replicated.  4:2:0:
+ *              s = 3 c[y] + c[y -+ 1] (row 2y the row above, row 2y + 1 the row below), out[2x] =
+ *              (3 s[x] + s[x - 1] + 8) >> 4, out[2x + 1] = (3 s[x] + s[x + 1] + 7) >> 4.  4:2:2: out[2x] =
+ *              (3 c[x] + c[x - 1] + 1) >> 2, out[2x + 1] = (3 c[x] + c[x + 1] + 2) >> 2.  A chroma plane of
+ *              cw <= 2 is replicated, not filtered (libjpeg switches filters there);
+ *   colour     with cb, cr minus 128: R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *              G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), each clamped to 0..255.
+ * Pixel (y, x) of frame b goes to out + b * frame_stride_bytes + y * pitch_bytes + 3 x, channels R G B (bgr 0) or
+ * B G R (bgr 1); no byte outside rows of 3 w bytes is written.  status[b]: 0; 1 a bit pattern that is no code (or a
+ * DC category above 11), 2 a zero run past coefficient 63, 3 an interval whose data ends early, 4 an intervals /
+ * frame_first / set_index entry out of range; the largest of a frame's intervals.  Such an interval ends there:
+ * frame b's pixels are then unspecified but stay inside its slot, and the other frames are unaffected.
+ * split: 0 one wave per interval (the default), 1 one lane per interval (profiles/mjpeg_decode_micro.txt).
+ * Stream-ordered, no host synchronisation.  n, h, w <= 65535; ws >= s2v_jpeg_decode_ws_bytes(n, h, w, sampling)
+ * bytes, 16-byte aligned (int16 coefficients [n][mcu][blocks][64] and the three planes at MCU-padded sizes);
+ * every array is device memory. */
+int s2v_jpeg_decode(const uint8_t *data, long data_bytes, const int *intervals, int n_intervals,
+                    const int *frame_first, int max_per_frame, int n, int h, int w, int sampling,
+                    const uint16_t *qtables, const uint8_t *huff_sets, int n_sets, const int *set_index, uint8_t *out,
+                    long pitch_bytes, long frame_stride_bytes, int bgr, int *status, void *ws, long ws_bytes, int split,
+                    s2v_stream_t stream);
+long s2v_jpeg_decode_ws_bytes(int n, int h, int w, int sampling);
 /* cv2.warpAffine(src, M, (ow, oh), flags=INTER_LINEAR or INTER_AREA, BORDER_CONSTANT 0) on n HWC
  * images (dtype 0 uint8, 1 fp32, 2 fp64; pitches in elements): M = n device 2x3 fp64 forward
  * matrices, inverted on the device (invertAffineTransform); OpenCV's fixed-point source coordinates

@@ -8,9 +8,12 @@ Steps (reference file:line in brackets):
   * audio: stdlib ``wave`` PCM -> float32, channels averaged, resampled to 16 kHz
     (audio.load_wav = librosa.load(path, sr=16000), futils/audio.py:10-11) -> mel on the device ->
     16-column windows at 80 / fps columns per frame [inference.py:204-216];
-  * video: the MP4 header gives frame size, fps and frame count; there is no video decoder in this
-    image (no cv2 / ffmpeg), so the frames are synthetic uint8 BGR frames of that size (SURVEY.md
-    §8d allows this), or an .npy [N,H,W,3] uint8 array given as --face;
+  * video: --face NAME.avi is a Motion-JPEG AVI (``ffmpeg -i in.mp4 -c:v mjpeg -q:v 2 out.avi``): s2v_amd.mjpeg
+    reads the container and decodes the frames on the device (JpegDecoder, batches of --LNet_batch_size), fps from
+    the header; --face NAME.jpg is the reference's static mode [inference.py:58-64, :371]: the one frame for every
+    mel window, at --fps.  There is no MP4 decoder: of an MP4 the header gives frame size, fps and frame count and
+    the frames are synthetic uint8 BGR frames of that size (SURVEY.md §8d allows this); an .npy [N,H,W,3] uint8
+    array is taken as it is;
   * frames truncated to the number of mel windows [inference.py:219-221];
   * the face box: by default the centred square of --box_frac of the short side; with --face_det the
     reference's face_detect [inference.py:357, futils/inference_utils.py:110-148] on the device
@@ -200,6 +203,25 @@ def _frames(face: str, max_frames: int):
         f"synthetic {info['width']}x{info['height']} (no decoder; {info['frames']} frames in the file)"
 
 
+def decode_jpeg_frames(files, dev, batch: int = 16, first: int = 0) -> torch.Tensor:
+    """JPEG files of one size and sampling -> uint8 BGR [n, H, W, 3] on ``dev``, decoded there in batches of
+    ``batch`` (mjpeg.JpegDecoder): the frames never exist on the host.  A damaged stream raises ValueError naming
+    its frame (``first``: the number of files[0] in the clip)."""
+    from . import mjpeg
+    info = mjpeg.parse_jpeg(files[0])
+    dec = mjpeg.JpegDecoder(info.h, info.w, info.sampling, order="bgr", device=dev)
+    out = torch.empty((len(files), info.h, info.w, 3), dtype=torch.uint8, device=dev)
+    status = []
+    for s in range(0, len(files), max(1, batch)):
+        status.append(dec.decode(files[s:s + max(1, batch)], out=out[s:s + max(1, batch)])[1])
+    bad = torch.cat(status).cpu().numpy()
+    if bad.any():
+        k = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"frame {first + k}: damaged JPEG stream (decoder status {int(bad[k])}; "
+                         f"{int((bad != 0).sum())} of {len(files)} frames)")
+    return out
+
+
 # face3d's 5-point 3D reference when BFM/similarity_Lm3D_all.mat is absent (stated stand-in, the
 # layout of lm3d_from_68: eyes, nose tip, mouth corners)
 LM3D_STANDIN = np.array([[-0.31, 0.29, 0.41], [0.31, 0.29, 0.41], [0.0, 0.0, 0.65], [-0.25, -0.36, 0.44],
@@ -381,7 +403,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None,
         landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None,
         up_face: str = "original", without_rl1: bool = False, up_face_model=None, precision: str | None = None,
-        nms: str | None = "host"):
+        nms: str | None = "host", fps: float = 25.0):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -409,7 +431,11 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     opt-in "f16" (single-pass f16 products) is outside the fp32 parity bar: about 0.5 grey level on average.
     ``nms``: where the greedy NMS of every detector this call builds runs (S3FD, and RetinaFace in
     FaceEnhancement and GFPGANer): "host" (the default), "device" (face.nms_device; equal scores take the larger
-    position index first) or None for S2V_NMS; given detectors keep their own.  ``meta["nms"]`` records it."""
+    position index first) or None for S2V_NMS; given detectors keep their own.  ``meta["nms"]`` records it.
+    ``face``: NAME.avi (Motion-JPEG: the frames are decoded on the device in batches of ``batch`` and stay there, fps
+    from the header, ``meta["video"]`` "avi mjpeg WxH"; a damaged frame raises ValueError naming it), NAME.jpg /
+    .jpeg (the reference's static mode: the one frame for every mel window up to ``max_frames``, at ``fps``), an MP4
+    (header only: synthetic frames) or an .npy array.  ``fps`` is used for a static image only."""
     kw = dict(locals())                                     # the arguments (nothing else is bound yet)
     from . import audio, ops, pipeline, post, synth
     from . import face as faces
@@ -423,12 +449,32 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         ganimation.check_up_face(up_face)                  # ValueError before anything runs
     dev = torch.device(device)
     t0 = time.time()
-    frames_np, fps, src_kind = _frames(face, max_frames)
+    kind = os.path.splitext(face)[1].lower()
+    if kind == ".avi":
+        from . import mjpeg
+        reader = mjpeg.AviReader(face)                     # ValueError on a codec that is not Motion-JPEG
+        fps, available = reader.fps, min(len(reader), max_frames)
+    elif kind in (".jpg", ".jpeg"):
+        available = max_frames                             # the reference's static mode (inference.py:58-64, :371)
+    else:
+        frames_np, fps, src_kind = _frames(face, max_frames)
+        available = len(frames_np)
     wav = load_wav(audio_path, 16000)
     mel = audio.melspectrogram(torch.from_numpy(wav).to(dev))
     chunks = audio.mel_chunks(mel, fps=fps)
-    n = min(len(frames_np), chunks.shape[0])                                        # inference.py:219-221
-    frames = torch.from_numpy(np.ascontiguousarray(frames_np[:n])).to(dev)
+    n = min(available, chunks.shape[0])                                             # inference.py:219-221
+    if kind == ".avi":
+        if n == 0:
+            raise ValueError(f"{face}: no frames")
+        frames = decode_jpeg_frames(reader.frames(0, n), dev, batch)
+        src_kind = f"avi mjpeg {frames.shape[2]}x{frames.shape[1]}"
+    elif kind in (".jpg", ".jpeg"):
+        with open(face, "rb") as f:
+            one = decode_jpeg_frames([f.read()], dev)
+        frames = one.repeat(n, 1, 1, 1)                                             # one frame for every window
+        src_kind = f"jpeg {one.shape[2]}x{one.shape[1]} (static)"
+    else:
+        frames = torch.from_numpy(np.ascontiguousarray(frames_np[:n])).to(dev)
     H, W = frames.shape[1:3]
     side = int(min(H, W) * box_frac)
     y1, x1 = (H - side) // 2, (W - side) // 2
@@ -541,7 +587,10 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
 
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--face", required=True, help="MP4 (header read; synthetic frames) or uint8 [N,H,W,3] .npy")
+    ap.add_argument("--face", required=True,
+                    help="Motion-JPEG .avi (decoded on the device), one .jpg / .jpeg (static: the frame repeats), MP4 "
+                         "(header read; synthetic frames) or uint8 [N,H,W,3] .npy")
+    ap.add_argument("--fps", type=float, default=25.0, help="with --face NAME.jpg: frames per second of the clip")
     ap.add_argument("--audio", required=True, help="PCM .wav")
     ap.add_argument("--outfile", default="results/inference_frames.npz",
                     help="NAME.avi: a Motion-JPEG AVI of the frames (the --enhance output when there is one) with the "
@@ -606,7 +655,7 @@ def main(argv=None):
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
             nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
             stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1, precision=a.precision,
-            nms=a.nms)
+            nms=a.nms, fps=a.fps)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     if a.outfile.lower().endswith(".avi"):
         video = r["enhanced"] if r["enhanced"] is not None else r["frames"]
