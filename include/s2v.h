@@ -302,9 +302,28 @@ int s2v_resize(const float *x, int n, int c, int ih, int iw, long long xsn, long
  *   y[b,p,3] = up2(skip)[b,p,3]
  * x NHWC [n][h][w] (pixel pitch xcs, c % 32 == 0), wt packed 1x1 rows [3+][kpad], s [n][s_ns], bias [3]
  * or NULL, skip NHWC [n][h/2][w/2] (pitch skcs >= 4), y NHWC [n][h][w] (pitch ycs >= 4); up2 is
- * F.interpolate(scale_factor=2, mode='bilinear', align_corners=False).  h*w % 32 == 0. */
+ * F.interpolate(scale_factor=2, mode='bilinear', align_corners=False). */
 int s2v_torgb_up2(const float *x, int n, int h, int w, int c, int xcs, const float *wt, int kpad, const float *s,
                   int s_ns, const float *bias, const float *skip, int skcs, float *y, int ycs, s2v_stream_t stream);
+
+/* The same pass on a window of a larger frame, for a consumer that crops the frame's border (ENet's
+ * [8:-8, 8:-8]): x / y hold the h x w output pixels whose pixel (0, 0) is frame pixel (oy, ox) of the
+ * fh x fw output frame, skip the sh x sw pixels whose pixel (0, 0) is pixel (sy, sx) of the fh/2 x fw/2
+ * skip frame.  The bilinear taps and weights are those of the pixel's frame position, so a pixel gets
+ * bit for bit the value the whole-frame call gives it; a window whose taps leave the skip window is
+ * refused.  fh = fw = 0: the window is the frame.  nchw != 0: y is instead the contiguous
+ * [n][3][h - 2 cy][w - 2 cx] planes of channels 0..2 with cy rows / cx columns cropped off each side
+ * (the closing NHWC -> NCHW transpose of the ENet tail done by the store). */
+typedef struct s2v_torgb_win {
+    int fh, fw;
+    int oy, ox;
+    int sh, sw;
+    int sy, sx;
+    int nchw, cy, cx;
+} s2v_torgb_win;
+int s2v_torgb_up2_win(const float *x, int n, int h, int w, int c, int xcs, const float *wt, int kpad, const float *s,
+                      int s_ns, const float *bias, const float *skip, int skcs, float *y, int ycs,
+                      const s2v_torgb_win *win, s2v_stream_t stream);
 
 /* Row-tap packing of a small-channel input for a kh x kw conv (r04): y[n][h][w][dx * c + ci] =
  * x[n][h][w + dx - pw][ci] (zero outside the row), channels [kw * c, ycs) zero; the conv then runs as

@@ -207,12 +207,13 @@ static bool cpar_lw(int co, int K, long long w_bs, int batch, int M, int tpp) {
 static int cpar_lanes(int cin) { return cin >= 128 ? 8 : cin >= 64 ? 4 : cin >= 32 ? 2 : 4; }
 
 // 4-channel 1x1 / 3x3 convs on the exact-fp32 MFMA kernel (conv_k4.hip) in every precision mode: stride 1,
-// zero "same" padding, 32k <= 256 output channels, a plain epilogue (scale, shift, per-pixel add, activation)
+// zero "same" padding or none (the kernel bounds-checks every tap against the input, so the unpadded conv is the
+// padded one's interior), 32k <= 256 output channels, a plain epilogue (scale, shift, per-pixel add, activation)
 static bool k4_ok(const s2v_conv_params *p) {
     if (!k4_on() || p->cin != 4 || p->kh != p->kw || (p->kh != 1 && p->kh != 3) || p->force_tile || p->b_kn || p->x_split)
         return false;
     if (p->in_mode != S2V_IN_DIRECT || p->pad_mode != S2V_PAD_ZERO || p->sh != 1 || p->sw != 1 || p->dh != 1 ||
-        p->dw != 1 || p->ph != p->kh / 2 || p->pw != p->kw / 2)
+        p->dw != 1 || !((p->ph == p->kh / 2 && p->pw == p->kw / 2) || (p->ph == 0 && p->pw == 0)))
         return false;
     if (p->cout % 32 || p->cout > 256 || p->in_scale || p->pre_act != S2V_ACT_NONE || p->nc_scale || p->res ||
         p->post_mul || p->dup_src || p->out_pool || p->out_step > 1 || p->d2s_cout > 0)

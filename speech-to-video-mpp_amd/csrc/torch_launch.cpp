@@ -747,21 +747,49 @@ void pad_reflect_(const Tensor &x, const Tensor &y, at::IntArrayRef pads) {
 
 // ToRGB + x2 bilinear skip upsample (s2v_torgb_up2): x NHWC view [N, H, W, C], wt packed 1x1 rows
 // [>= 3, kpad], s [N, >= C] row view, bias [3] or None, skip NHWC [N, H/2, W/2, >= 4], y NHWC [N, H, W, >= 4]
+// ``window`` (s2v_torgb_win): empty = x / y are the whole frame; (fh, fw, oy, ox, sy, sx) = x / y are the window at
+// (oy, ox) of the fh x fw output frame and skip [N, SH, SW, 4] the window at (sy, sx) of the fh/2 x fw/2 skip frame.
+// ``crop`` (cy, cx): y is the contiguous NCHW tensor [N, 3, H - 2 cy, W - 2 cx] instead of an NHWC view.
 void torgb_up2_(const Tensor &x, const Tensor &wt, const Tensor &s, const OptT &bias, const Tensor &skip,
-                const Tensor &y) {
+                const Tensor &y, at::IntArrayRef window, at::IntArrayRef crop) {
     const c10::DeviceGuard guard(x.device());
     const at::Device dev = x.device();
-    const NV xv = nhwc(x, dev, "torgb x"), kv = nhwc(skip, dev, "torgb skip"), yv = nhwc(y, dev, "torgb y");
+    const NV xv = nhwc(x, dev, "torgb x"), kv = nhwc(skip, dev, "torgb skip");
     f32(wt, dev, "torgb wt");
     TORCH_CHECK(wt.dim() == 2 && wt.is_contiguous() && wt.size(0) >= 3 && wt.size(1) >= xv.c,
                 "torgb wt: packed 1x1 rows [>= 3, kpad >= C]");
     const int s_ns = (int)rows_view(s, dev, xv.n, xv.c, "torgb s");
     const float *bp = vec(bias, dev, 3, "torgb bias");
-    TORCH_CHECK(kv.n == xv.n && yv.n == xv.n && yv.h == xv.h && yv.w == xv.w && 2 * kv.h == xv.h && 2 * kv.w == xv.w &&
-                    kv.c == 4 && yv.c == 4,
-                "torgb: skip [N, H/2, W/2, 4] and y [N, H, W, 4] views expected");
-    check(s2v_torgb_up2(xv.p, xv.n, xv.h, xv.w, xv.c, xv.cs, wt.data_ptr<float>(), (int)wt.size(1), s.data_ptr<float>(),
-                        s_ns, bp, kv.p, kv.cs, yv.p, yv.cs, stream()),
+    TORCH_CHECK(window.empty() || window.size() == 6, "torgb window: (fh, fw, oy, ox, sy, sx) or empty");
+    TORCH_CHECK(crop.empty() || crop.size() == 2, "torgb crop: (cy, cx) or empty");
+    TORCH_CHECK(kv.n == xv.n && kv.c == 4, "torgb: skip [N, SH, SW, 4] view expected");
+    s2v_torgb_win win{};
+    win.sh = kv.h; win.sw = kv.w;
+    if (window.empty()) {
+        TORCH_CHECK(2 * kv.h == xv.h && 2 * kv.w == xv.w, "torgb: skip [N, H/2, W/2, 4] expected");
+        win.fh = xv.h; win.fw = xv.w;
+    } else {
+        for (int64_t v : window) TORCH_CHECK(v >= 0 && v < (1 << 30), "torgb window: bad value ", v);
+        win.fh = (int)window[0]; win.fw = (int)window[1]; win.oy = (int)window[2]; win.ox = (int)window[3];
+        win.sy = (int)window[4]; win.sx = (int)window[5];
+    }
+    float *yp = nullptr;
+    int ycs = 0;
+    if (crop.empty()) {
+        const NV yv = nhwc(y, dev, "torgb y");
+        TORCH_CHECK(yv.n == xv.n && yv.h == xv.h && yv.w == xv.w && yv.c == 4, "torgb: y [N, H, W, 4] view expected");
+        yp = yv.p; ycs = yv.cs;
+    } else {
+        f32(y, dev, "torgb y");
+        TORCH_CHECK(crop[0] >= 0 && crop[1] >= 0 && 2 * crop[0] < xv.h && 2 * crop[1] < xv.w, "torgb crop: bad (cy, cx)");
+        win.nchw = 1; win.cy = (int)crop[0]; win.cx = (int)crop[1];
+        TORCH_CHECK(y.dim() == 4 && y.is_contiguous() && y.size(0) == xv.n && y.size(1) == 3 &&
+                        y.size(2) == xv.h - 2 * win.cy && y.size(3) == xv.w - 2 * win.cx,
+                    "torgb: contiguous NCHW y [N, 3, H - 2 cy, W - 2 cx] expected, got ", y.sizes());
+        yp = y.data_ptr<float>();
+    }
+    check(s2v_torgb_up2_win(xv.p, xv.n, xv.h, xv.w, xv.c, xv.cs, wt.data_ptr<float>(), (int)wt.size(1),
+                            s.data_ptr<float>(), s_ns, bp, kv.p, kv.cs, yp, ycs, &win, stream()),
           "s2v_torgb_up2");
 }
 
@@ -1111,7 +1139,8 @@ TORCH_LIBRARY_FRAGMENT(s2v, m) {
           "int[4] y_stride, float scale_h, float scale_w, int mode) -> ()");
     m.def("pad_reflect_(Tensor x, Tensor(a!) y, int[4] pads) -> ()");
     m.def("row_pack_(Tensor x, Tensor(a!) y, int kw, int pw) -> ()");
-    m.def("torgb_up2_(Tensor x, Tensor wt, Tensor s, Tensor? bias, Tensor skip, Tensor(a!) y) -> ()");
+    m.def("torgb_up2_(Tensor x, Tensor wt, Tensor s, Tensor? bias, Tensor skip, Tensor(a!) y, int[] window, "
+          "int[] crop) -> ()");
     m.def("flow_warp_(Tensor flow, Tensor src, Tensor(a!) y) -> ()");
     m.def("flow_warp_cat_(Tensor flow, Tensor src, Tensor(a!) y) -> ()");
     m.def("fill_value_(Tensor(a!) y, float value) -> ()");

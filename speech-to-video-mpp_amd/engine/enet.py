@@ -61,6 +61,46 @@ PREMOD = os.environ.get("S2V_ENET_PREMOD", "1") == "1"
 STACK_STRIPS = os.environ.get("S2V_ENET_STACK_STRIPS", "1") == "1"
 # persistent blocks of the resumed part (S2V_ENET_RESUME_GRID; default: as STYLE_GRID)
 RESUME_GRID = os.environ.get("S2V_ENET_RESUME_GRID", "")
+# the StyleConv tail computed only on the pixels that can reach the output ENet keeps ([:, :, 8:-8, 8:-8]):
+# every conv unpadded on a dense, smaller tensor (crop_tail_cone), no polyphase edge strips, ToRGB1 storing the
+# cropped NCHW output itself.  Kept pixels are bit for bit those of the full-frame tail.  S2V_ENET_CROP_TAIL=0:
+# the full-frame tail
+CROP_TAIL = os.environ.get("S2V_ENET_CROP_TAIL", "1") == "1"
+OUT_CROP = 8                 # ENet.py:139
+
+
+def crop_tail_cone(size: int, crop: int):
+    """Dependency cone of the tail's output rows ``crop .. 4 size - 1 - crop`` (columns alike) for a ``size``^2
+    tail input, and the windows the unpadded chain computes.  Returns None when the full-frame tail is needed,
+    else {"need": {layer: (first, last)}, "win": {layer: (origin, size)}, "crop": c, "out": n}: frame rows, in
+    the layer's own frame (2 size for conv1 / conv2 / rgb0, 4 size for conv3 / conv4 / rgb1), ``c`` the rows
+    ToRGB1's store still crops off each side of its window and ``n`` the output size.
+
+    need, from the output back: ToRGB1 and StyleConv 4 (3x3) the kept rows; StyleConv 3 one more row per side;
+    its polyphase form reads input pixel r // 2 for output row r, and that pixel's 3x3 neighbourhood of StyleConv
+    2's output; StyleConv 1 one more row again.  rgb0 is read by ToRGB1's x2 skip upsample: the bilinear taps
+    (align_corners=False) of the kept rows.  The polyphase fold is exact on every output row but the frame's
+    outermost two per side (_poly_styleconv), so the cone stays clear of them iff crop >= 3.
+    win: x0 = up2(input) is the whole 2 size frame; each unpadded 3x3 conv loses one row per side, the polyphase
+    conv over h rows gives 2 (h - 2) rows starting at twice (its input's origin + 1).  The chain serves the crop
+    when every layer's need lies in its window; ENet's crop of 8 is the case it is built for."""
+    f1, f2 = 2 * size, 4 * size
+    lo, hi = crop, f2 - 1 - crop
+    if crop < 3 or lo > hi:
+        return None
+    need = {"rgb1": (lo, hi), "conv4": (lo, hi), "conv3": (lo - 1, hi + 1)}
+    p0, p1 = (lo - 1) // 2, (hi + 1) // 2
+    need["conv2"] = (p0 - 1, p1 + 1)
+    need["conv1"] = (p0 - 2, p1 + 2)
+    # up2 taps of rows lo / hi: src = r / 2 - 0.25 -> rows floor(src), floor(src) + 1 (away from the frame border)
+    need["rgb0"] = ((2 * lo - 1) // 4, (2 * hi - 1) // 4 + 1)
+    win = {"conv1": (1, f1 - 2), "conv2": (2, f1 - 4), "rgb0": (2, f1 - 4), "conv3": (6, f2 - 12),
+           "conv4": (7, f2 - 14), "rgb1": (7, f2 - 14)}
+    for k, (a, b) in need.items():
+        o, n = win[k]
+        if n <= 0 or a < o or b > o + n - 1:
+            return None
+    return {"need": need, "win": win, "crop": crop - 7, "out": f2 - 2 * crop}
 
 
 def style_grid(device) -> int:
@@ -190,9 +230,10 @@ class ENetEngine:
         ops.modconv_demod_rows(ctx, s2, t, dall, eps=1e-8, post=math.sqrt(2.0))
         return t, dall
 
-    def _premodulate(self, ctx, s2, dtab, dall, b) -> dict:
+    def _premodulate(self, ctx, s2, dtab, dall, b, strips=True) -> dict:
         """PREMOD: the per-sample weights of the tail's StyleConvs, {layer index: {"conv4" / "conv": (wbuf,
-        premod)}} (row-packed layers keep their in-launch modulation)."""
+        premod)}} (row-packed layers keep their in-launch modulation).  ``strips``: a polyphase layer's direct
+        form too, for its edge strips (the cropped tail runs none)."""
         wb = {}
         for st in range(2):
             for li in range(2):
@@ -204,8 +245,9 @@ class ENetEngine:
                     continue      # the 4-channel first StyleConv runs exact fp32 (conv_k4.hip): modulated in-launch
                 if POLY_UP and L.conv4 is not None:
                     d4 = dall[:, r0: r0 + wd]
-                    wb[idx] = {"conv4": ops.modulate_weights(ctx, L.conv4, sv, d4, b),
-                               "conv": ops.modulate_weights(ctx, L.conv, sv, d4[:, : L.cout], b)}
+                    wb[idx] = {"conv4": ops.modulate_weights(ctx, L.conv4, sv, d4, b)}
+                    if strips:
+                        wb[idx]["conv"] = ops.modulate_weights(ctx, L.conv, sv, d4[:, : L.cout], b)
                 elif L.rp is None:
                     wb[idx] = {"conv": ops.modulate_weights(ctx, L.conv, sv, dall[:, r0: r0 + L.cout], b)}
         return wb
@@ -215,9 +257,13 @@ class ENetEngine:
         the modulated 3x3 conv + noise + bias + LeakyReLU, as one depth-to-space conv over ``cur`` with
         the folded parity-class filters (L.conv4).  The fold assumes every upsampled row / column is an
         interior one: the clamped edge rows of the upsample and the conv's zero padding break that on
-        the two outermost output lines of each side, so those are recomputed from 2-pixel strips of
-        ``cur`` the direct way (upsample + conv with L.conv; every tap they read is exact) and copied
-        in."""
+        the two outermost output lines of each side (lines 0, 1, 2h - 2 and 2h - 1), so those are recomputed
+        from 2-pixel strips of ``cur`` the direct way (upsample + conv with L.conv; every tap they read is
+        exact) and copied in.  Per axis that is a strip gather, an upsample, a noise gather, a conv on a
+        13-block grid and two copies: twelve launches and ~0.45 ms of the B = 16 tail for four lines that
+        only feed the next StyleConv's rows 0..2 and its last three.  A consumer that crops at least 3
+        output pixels never sees them: ENet's tail takes _cropped_tail (CROP_TAIL) and runs no strips;
+        this full-frame form stays for S2V_ENET_CROP_TAIL=0 and for callers that keep the whole frame."""
         dev, b = self.device, cur.n
         h2, w2 = 2 * cur.h, 2 * cur.w
         d = d4[:, : L.cout]                                      # the class-0 block: the layer's own demod
@@ -268,6 +314,81 @@ class ENetEngine:
             ysel(y.t).copy_(ssel(ys.t))
         return y
 
+    def _crop_cone(self, size, out):
+        """crop_tail_cone of the forward when the cropped tail applies (CROP_TAIL, the default tail configuration
+        it is written for: fused ToRGB, polyphase second stage, direct first StyleConv), else None."""
+        L = self.layers
+        if not (CROP_TAIL and POLY_UP and FUSED_TORGB) or L[0].conv4 is not None or L[0].rp is not None or \
+                L[3].conv4 is None or L[1].conv4 is not None or L[4].conv4 is not None or L[2].cin % 32 or L[5].cin % 32:
+            return None
+        cone = crop_tail_cone(size, OUT_CROP)
+        if cone is not None and tuple(out.shape[1:]) != (3, cone["out"], cone["out"]):
+            return None
+        return cone
+
+    def _noise_window(self, ctx, L, idx, b, frame, origin, n, noises, ctr):
+        """The [B, n, n] window at ``origin`` of StyleConv ``idx``'s noise plane, drawn (or passed by the caller)
+        as the whole [B, frame, frame] plane with the full-frame tail's seed and counter; None without noise."""
+        if not L.noise_w:
+            return None
+        if noises is not None and noises[idx] is not None:
+            plane = noises[idx].reshape(b, frame, frame)
+        else:
+            plane = torch.empty((b, frame, frame), device=self.device)
+            ops.gaussian_noise(ctx, plane, self.noise_seed, idx << 36, ctr=ctr, shift=40)
+            self.last_noises[idx] = plane
+        return plane[:, origin: origin + n, origin: origin + n].contiguous()
+
+    def _cropped_tail(self, ctx, cur: NHWC, s2, dtab, dall, wbs, noises, ctr, out, cone):
+        """The two StyleGAN2 stages (ENet.py:119-129) on the windows of crop_tail_cone: every StyleConv unpadded
+        over its input window (the padded conv's interior: the same taps in the same order, on the same tile
+        family), the second stage's polyphase conv without edge strips (no output line it computes is one the
+        fold gets wrong), the ToRGBs with their skip upsample addressed in frame coordinates, and ToRGB1 storing
+        the cropped NCHW ``out`` directly."""
+        dev, b, win = self.device, cur.n, cone["win"]
+        f1, f2 = 2 * cur.h, 4 * cur.h
+        L = self.layers
+        kw = dict(act=ops.ACT_LRELU, alpha=LRELU, padding=(0, 0))
+
+        def mod(j):                                  # layer j's modulation segment; a StyleConv's demod slot and
+            sv = s2[:, self.mod_offs[j]: self.mod_offs[j] + L[j].cin]               # premod weights too
+            if L[j].is_rgb:
+                return sv, None, {}
+            idx = j - j // 3
+            return sv, dtab.r0[idx], wbs.get(idx, {})
+
+        x = NHWC.empty(b, f1, f1, cur.c, dev)
+        ops.resize_nhwc(ctx, cur, x, scale_factor=2)
+        for j, name in ((0, "conv1"), (1, "conv2")):
+            o, n = win[name]
+            s, r0, wb = mod(j)
+            y = NHWC.empty(b, n, n, L[j].cout, dev)
+            ops.modulated_conv2d(ctx, x, L[j].conv, y, s, dall[:, r0: r0 + L[j].cout], pix_w=L[j].noise_w or 0.0,
+                                 pix_add=self._noise_window(ctx, L[j], j, b, f1, o, n, noises, ctr),
+                                 premod=wb.get("conv"), **kw)
+            x = y
+        o, n = win["rgb0"]
+        rgb0 = NHWC.empty(b, n, n, 4, dev)
+        ops.torgb_up2(ctx, x, L[2].conv, mod(2)[0], cur, rgb0, frame=(f1, f1), origin=(o, o))
+        o3, n3 = win["conv3"]
+        s, r0, wb = mod(3)
+        y = NHWC.empty(b, n3, n3, L[3].cout, dev)
+        ops.modulated_conv2d(ctx, x, L[3].conv4, y, s, dall[:, r0: r0 + dtab.width[2]], d2s=True,
+                             pix_w=L[3].noise_w or 0.0,
+                             pix_add=self._noise_window(ctx, L[3], 2, b, f2, o3, n3, noises, ctr),
+                             premod=wb.get("conv4"), **kw)
+        o4, n4 = win["conv4"]
+        s, r0, wb = mod(4)
+        z = NHWC.empty(b, n4, n4, L[4].cout, dev)
+        ops.modulated_conv2d(ctx, y, L[4].conv, z, s, dall[:, r0: r0 + L[4].cout], pix_w=L[4].noise_w or 0.0,
+                             pix_add=self._noise_window(ctx, L[4], 3, b, f2, o4, n4, noises, ctr),
+                             premod=wb.get("conv"), **kw)
+        dst = out if out.is_contiguous() else torch.empty(out.shape, device=dev)
+        ops.torgb_up2(ctx, z, L[5].conv, mod(5)[0], rgb0, dst, frame=(f2, f2), origin=(o4, o4), skip_origin=(o, o),
+                      crop=(cone["crop"], cone["crop"]))
+        if dst is not out:
+            out.copy_(dst)
+
     def style_code(self, ctx, ref: torch.Tensor):
         """ref: NCHW [B,3,H,W] device tensor -> style [B,1,1,512] (ENet.py:94-101)."""
         st = self.style_begin(ctx, ref)
@@ -314,6 +435,7 @@ class ENetEngine:
         b = audio.shape[0]
         svec = NHWC.empty(b, 1, 1, self.mod.cout, dev)
         side = self._side(ctx) if OVERLAP else None
+        cone = self._crop_cone(96 + 4, out)          # the cropped tail's windows, None: the full-frame tail
         enc = {}
 
         def finish(sctx):
@@ -321,7 +443,8 @@ class ENetEngine:
             ops.conv2d(sctx, enc["style"], self.mod, svec)
             enc["d"] = self._demods(sctx, svec.t.view(b, -1))       # off the tail: beside LNet
             if PREMOD:
-                enc["wb"] = self._premodulate(sctx, svec.t.view(b, -1), enc["d"][0], enc["d"][1], b)
+                enc["wb"] = self._premodulate(sctx, svec.t.view(b, -1), enc["d"][0], enc["d"][1], b,
+                                              strips=cone is None)
 
         def fork():
             sst, sctx = side
@@ -382,6 +505,9 @@ class ENetEngine:
         self.last_noises = [None] * 4
         if noises is None and any(L.noise_w for L in self.layers):
             ctr = ctx.noise(id(self)).bump(ctx)        # one draw per forward, also under graph replay
+        if cone is not None:
+            self._cropped_tail(ctx, cur, s2, dtab, dall, enc.get("wb", {}), noises, ctr, out, cone)
+            return out, low
         for st in range(2):
             for li in range(2):
                 L = self.layers[3 * st + li]

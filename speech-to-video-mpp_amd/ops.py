@@ -850,7 +850,7 @@ def modulate_weights(ctx: Ctx, cw: ConvW, s: torch.Tensor, d: torch.Tensor | Non
 
 def modulated_conv2d(ctx: Ctx, x: NHWC, cw: ConvW, y: NHWC, s: torch.Tensor, d: torch.Tensor | None = None, *,
                      act=ACT_NONE, alpha=0.0, res: NHWC | None = None, res_after=False, pix_add=None, pix_w=0.0,
-                     shift=None, force_splits=0, d2s=False, premod=None):
+                     shift=None, force_splits=0, d2s=False, premod=None, padding=None, force_tile=0):
     """StyleGAN2 modulated conv with per-sample weights W * s[b, c] (* d[b, o]) written by the
     ``s2v::modulated_conv2d_`` op in the form its planned kernel reads (split layout with a 2^11 f16
     pre-scale when demodulated, or fp32), then one batched conv (no prologue / epilogue scaling in
@@ -858,8 +858,15 @@ def modulated_conv2d(ctx: Ctx, x: NHWC, cw: ConvW, y: NHWC, s: torch.Tensor, d: 
     ``d2s``: cw holds the 4 parity classes of a x2-upsampled conv (cout = 4 classes x c, class-major)
     and y is the full [B, 2H, 2W, c] output (s2v_conv_params.d2s_cout); pix_add is then [B, 2H, 2W].
     ``premod``: a (wbuf, premod) pair from modulate_weights for the same (cw, s, d): the conv reads those weights
-    instead of modulating them again (the op refuses a layout its plan does not read)."""
+    instead of modulating them again (the op refuses a layout its plan does not read).
+    ``padding``: (ph, pw) instead of cw's own, on the same packed weights (and so the same ``premod`` buffers):
+    padding 0 computes the interior of the padded conv, every kept pixel from the same taps in the same order.
+    ``force_tile``: the planner's tile (s2v_conv_params.force_tile) instead of its own or PERFDB's choice."""
+    ph, pw = (cw.ph, cw.pw) if padding is None else padding
     oh, ow = cw.out_hw(x.h, x.w)
+    if padding is not None:
+        assert cw.in_mode == IN_DIRECT, "modulated_conv2d: a padding override on direct inputs only"
+        oh, ow = x.h + 2 * ph - (cw.kh - 1), x.w + 2 * pw - (cw.kw - 1)
     assert cw.in_mode != IN_TRANSPOSED and cw.poly is None and (cw.sh, cw.sw, cw.dh, cw.dw) == (1, 1, 1, 1), \
         "modulated_conv2d: direct stride-1 convs only"
     if d2s:
@@ -880,14 +887,15 @@ def modulated_conv2d(ctx: Ctx, x: NHWC, cw: ConvW, y: NHWC, s: torch.Tensor, d: 
                             f"conv runs in {PRECISION!r} (code {prec})")
     sh = cw.shift if shift is None else shift            # the layer bias (epilogue shift) unless overridden
     xscale, flag = _range(ctx, cw, x, prec)
-    key, force_tile = None, 0
-    if (PERFDB or TUNE is not None) and prec != PREC_F32 and not (force_splits or x_split):
+    key = None
+    if (PERFDB or TUNE is not None) and prec != PREC_F32 and not (force_splits or x_split or force_tile) and \
+            padding is None:
         key = conv_key(x, cw, yv, 1, False, layout_code(prec)) + f"|mod{int(d is not None)}{int(d2s)}"
         if TUNE is None and perfdb_applies(x.t.device):
             force_tile, force_splits = PERFDB.get(key, (0, 0))
 
     def launch(ws, dry=False, st=_NOSTAMP, ft=None, fs=None):
-        return S2V.modulated_conv2d_(x.v, yv, cw.wt, s, d, wbuf, cw.cout, [cw.kh, cw.kw], [cw.ph, cw.pw], cw.in_mode,
+        return S2V.modulated_conv2d_(x.v, yv, cw.wt, s, d, wbuf, cw.cout, [cw.kh, cw.kw], [ph, pw], cw.in_mode,
                                      prec,
                                      x_split != 0, cw.scale, sh, pix_add, pix_w, resv, res_after, act, alpha, ws,
                                      force_splits if fs is None else fs, st[0], st[1], st[2], xscale, flag, dry, int(d2s),
@@ -1115,13 +1123,29 @@ def nhwc_to_nchw(ctx: Ctx, x: NHWC, out: torch.Tensor, crop=(0, 0)):
     return out
 
 
-def torgb_up2(ctx: Ctx, x: NHWC, cw: "ConvW", s: torch.Tensor, skip: NHWC, y: NHWC):
+def torgb_up2(ctx: Ctx, x: NHWC, cw: "ConvW", s: torch.Tensor, skip: NHWC, y, *, frame=None, origin=(0, 0),
+              skip_origin=(0, 0), crop=None):
     """ToRGB (1x1 modulated conv to 3 channels, no demodulation, + bias) plus the x2 bilinear
     upsample of ``skip`` in one pass (``s2v::torgb_up2_``, base_blocks.py:536-554).  skip / y carry 4
-    channels (the 4th is the upsampled skip's 4th).  s: [B, cin] row view."""
+    channels (the 4th is the upsampled skip's 4th).  s: [B, cin] row view.
+    ``frame`` = (fh, fw): x / y are the window at ``origin`` of that output frame and skip the window at
+    ``skip_origin`` of the (fh / 2, fw / 2) skip frame; the taps are the frame's, so a pixel gets the value the
+    whole-frame call gives it (the op refuses a window whose taps leave the skip window).
+    ``crop`` = (cy, cx): y is the contiguous NCHW tensor [B, 3, H - 2 cy, W - 2 cx] of channels 0..2 instead of
+    an NHWC view (the tail's closing transpose and crop done by the store)."""
     assert cw.kh == cw.kw == 1 and cw.cout == 3 and x.c == cw.cin, "torgb_up2: a 1x1 conv to 3 channels"
-    assert (y.n, y.h, y.w, y.c) == (x.n, x.h, x.w, 4) and (skip.n, 2 * skip.h, 2 * skip.w, skip.c) == (x.n, x.h, x.w, 4)
-    S2V.torgb_up2_(x.v, cw.wt, s, cw.shift, skip.v, y.v)
+    assert skip.n == x.n and skip.c == 4
+    if frame is None:
+        assert origin == (0, 0) and skip_origin == (0, 0) and (2 * skip.h, 2 * skip.w) == (x.h, x.w)
+        window = []
+    else:
+        window = [int(frame[0]), int(frame[1]), int(origin[0]), int(origin[1]), int(skip_origin[0]), int(skip_origin[1])]
+    if crop is None:
+        assert (y.n, y.h, y.w, y.c) == (x.n, x.h, x.w, 4)
+        S2V.torgb_up2_(x.v, cw.wt, s, cw.shift, skip.v, y.v, window, [])
+    else:
+        assert tuple(y.shape) == (x.n, 3, x.h - 2 * crop[0], x.w - 2 * crop[1])
+        S2V.torgb_up2_(x.v, cw.wt, s, cw.shift, skip.v, y, window, [int(crop[0]), int(crop[1])])
     return y
 
 

@@ -55,13 +55,14 @@ _LNET = [
 _ENET = [
     ("conv_k4_mfma<1,", _b(16 * 256 * 256 * 4 * F, 16 * 256 * 256 * 256 * F),
      "ENet conv_body_first 1x1 4->256 (ENet.py:94), exact fp32 MFMA: in 16x256^2x4, out 16x256^2x256"),
-    ("conv_k4_mfma<9,", _b(16 * 200 * 200 * 4 * F, 16 * 200 * 200 * F, 16 * 200 * 200 * 256 * F),
-     "ENet first StyleConv 3x3 4->256 at 200^2 (ENet.py:122), exact fp32 MFMA: in 16x200^2x4, noise 16x200^2, "
-     "out 16x200^2x256"),
-    ("torgb_up2_kernel<8, 4>", _b(16 * 400 * 400 * 128 * F, 16 * 200 * 200 * 4 * F, 16 * 400 * 400 * 4 * F),
-     "ENet 400^2 ToRGB + x2 skip (base_blocks.py:540-554): x 16x400^2x128, skip 16x200^2x4, out 16x400^2x4"),
-    ("torgb_up2_kernel<8, 2>", _b(16 * 200 * 200 * 256 * F, 16 * 100 * 100 * 4 * F, 16 * 200 * 200 * 4 * F),
-     "ENet 200^2 ToRGB + x2 skip: x 16x200^2x256, skip 16x100^2x4, out 16x200^2x4"),
+    ("conv_k4_mfma<9,", _b(16 * 200 * 200 * 4 * F, 16 * 198 * 198 * F, 16 * 198 * 198 * 256 * F),
+     "ENet first StyleConv 3x3 4->256, unpadded over the 200^2 frame (ENet.py:122; engine CROP_TAIL), exact fp32 "
+     "MFMA: in 16x200^2x4, noise 16x198^2, out 16x198^2x256"),
+    ("torgb_up2_kernel<8, 4>", _b(16 * 386 * 386 * 128 * F, 16 * 196 * 196 * 4 * F, 16 * 384 * 384 * 3 * F),
+     "ENet ToRGB + x2 skip on the 386^2 window (base_blocks.py:540-554), NCHW store of the kept 384^2: "
+     "x 16x386^2x128, skip 16x196^2x4, out 16x3x384^2"),
+    ("torgb_up2_kernel<8, 2>", _b(16 * 196 * 196 * 256 * F, 16 * 100 * 100 * 4 * F, 16 * 196 * 196 * 4 * F),
+     "ENet ToRGB + x2 skip on the 196^2 window: x 16x196^2x256, skip 16x100^2x4, out 16x196^2x4"),
 ]
 ALGO = {
     "dnet": _DNET,
