@@ -325,6 +325,27 @@ int s2v_torgb_up2_win(const float *x, int n, int h, int w, int c, int xcs, const
                       int s_ns, const float *bias, const float *skip, int skcs, float *y, int ycs,
                       const s2v_torgb_win *win, s2v_stream_t stream);
 
+/* x2 bilinear upsample + 3x3 conv (+ noise, bias, activation) from the nine 1x1 tap products of the
+ * un-upsampled input (ENet's StyleConv(sample_mode='upsample'), base_blocks.py:499-533).  The upsample is
+ * linear and per channel, so it commutes with a 1x1 channel mix:
+ *   conv3x3(up2(x))[r, c] = sum_{t = 3 dy + dx} up2(W_t x)[r + dy - 1, c + dx - 1]   (zero outside the frame)
+ *   y[b, r, c, o] = act(gain * that sum + bias[o] + pix_w * noise[b, r, c])
+ * p NHWC [n][ph][pw] with pixel pitch pcs >= 9 cout: channel t * cout + o is (W_t x)[o]; noise [n][oh][ow]
+ * or NULL, bias [cout] or NULL, y NHWC [n][oh][ow] (pitch ycs >= cout); cout % 4 == 0; act NONE / RELU /
+ * LRELU.  up2 is F.interpolate(scale_factor=2, mode='bilinear', align_corners=False).
+ * win: p is the window at (sy, sx) of the fh x fw low-resolution frame, y (and noise) the window at
+ * (oy, ox) of the 2 fh x 2 fw output frame; fh = fw = 0: p is the frame (fh = ph, fw = pw).  The taps,
+ * their edge clamp and the zero padding are the frame's, and every output is summed in one fixed order,
+ * so a pixel gets bit for bit the value of the whole-frame call; a window whose taps leave p is refused. */
+typedef struct s2v_tapsum_win {
+    int fh, fw;
+    int oy, ox;
+    int sy, sx;
+} s2v_tapsum_win;
+int s2v_tapsum_up2(const float *p, int n, int ph, int pw, int pcs, int cout, const float *noise, float pix_w,
+                   const float *bias, float gain, int act, float alpha, float *y, int oh, int ow, int ycs,
+                   const s2v_tapsum_win *win, s2v_stream_t stream);
+
 /* Row-tap packing of a small-channel input for a kh x kw conv (r04): y[n][h][w][dx * c + ci] =
  * x[n][h][w + dx - pw][ci] (zero outside the row), channels [kw * c, ycs) zero; the conv then runs as
  * a kh x 1 conv over ycs channels with the taps' weights at the same channel positions.  No

@@ -79,6 +79,8 @@ _SIGS = {
                                _c_int, _vp, _c_int, _vp]),
     "s2v_torgb_up2_win": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp,
                                    _c_int, _vp, _c_int, _vp, _vp]),
+    "s2v_tapsum_up2": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_float, _vp, _c_float, _c_int,
+                                _c_float, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     "s2v_resize": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _c_ll, _c_ll, _vp, _c_int, _c_int,
                             _c_ll, _c_ll, _c_ll, _c_ll, _c_float, _c_float, _c_int, _vp]),
     "s2v_row_pack": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp]),

@@ -793,6 +793,33 @@ void torgb_up2_(const Tensor &x, const Tensor &wt, const Tensor &s, const OptT &
           "s2v_torgb_up2");
 }
 
+// x2 bilinear upsample + 3x3 conv from the nine 1x1 tap products (s2v_tapsum_up2): p NHWC view [N, PH, PW, 9 C]
+// (tap-major), y NHWC view [N, OH, OW, C], noise contiguous [N, OH, OW] or None, bias [C] or None.
+// ``window`` (s2v_tapsum_win): empty = p is the whole low-resolution frame and y the whole 2 PH x 2 PW frame;
+// (fh, fw, oy, ox, sy, sx) = y is the window at (oy, ox) of the 2 fh x 2 fw frame and p the window at (sy, sx) of
+// the fh x fw frame.
+void tapsum_up2_(const Tensor &p, const OptT &noise, double pix_w, const OptT &bias, double gain, int64_t act,
+                 double alpha, const Tensor &y, at::IntArrayRef window) {
+    const c10::DeviceGuard guard(p.device());
+    const at::Device dev = p.device();
+    const NV pv = nhwc(p, dev, "tapsum p"), yv = nhwc(y, dev, "tapsum y");
+    TORCH_CHECK(yv.n == pv.n && pv.c == 9 * yv.c, "tapsum: p [N, PH, PW, 9 C] and y [N, OH, OW, C] views expected");
+    TORCH_CHECK(window.empty() || window.size() == 6, "tapsum window: (fh, fw, oy, ox, sy, sx) or empty");
+    s2v_tapsum_win win{};
+    if (window.empty()) {
+        TORCH_CHECK(yv.h == 2 * pv.h && yv.w == 2 * pv.w, "tapsum: y [N, 2 PH, 2 PW, C] expected");
+    } else {
+        for (int64_t v : window) TORCH_CHECK(v >= 0 && v < (1 << 29), "tapsum window: bad value ", v);
+        win.fh = (int)window[0]; win.fw = (int)window[1]; win.oy = (int)window[2]; win.ox = (int)window[3];
+        win.sy = (int)window[4]; win.sx = (int)window[5];
+    }
+    const float *np = vec(noise, dev, (int64_t)yv.n * yv.h * yv.w, "tapsum noise");
+    const float *bp = vec(bias, dev, yv.c, "tapsum bias");
+    check(s2v_tapsum_up2(pv.p, pv.n, pv.h, pv.w, pv.cs, yv.c, np, (float)pix_w, bp, (float)gain, (int)act, (float)alpha,
+                         yv.p, yv.h, yv.w, yv.cs, &win, stream()),
+          "s2v_tapsum_up2");
+}
+
 // flow NHWC view (>= 2 channels: x, y), src [N, C, H, W] (any strides), y NHWC view [N, H, W, C]
 void flow_warp_(const Tensor &flow, const Tensor &src, const Tensor &y) {
     const c10::DeviceGuard guard(flow.device());
@@ -1141,6 +1168,8 @@ TORCH_LIBRARY_FRAGMENT(s2v, m) {
     m.def("row_pack_(Tensor x, Tensor(a!) y, int kw, int pw) -> ()");
     m.def("torgb_up2_(Tensor x, Tensor wt, Tensor s, Tensor? bias, Tensor skip, Tensor(a!) y, int[] window, "
           "int[] crop) -> ()");
+    m.def("tapsum_up2_(Tensor p, Tensor? noise, float pix_w, Tensor? bias, float gain, int act, float alpha, "
+          "Tensor(a!) y, int[] window) -> ()");
     m.def("flow_warp_(Tensor flow, Tensor src, Tensor(a!) y) -> ()");
     m.def("flow_warp_cat_(Tensor flow, Tensor src, Tensor(a!) y) -> ()");
     m.def("fill_value_(Tensor(a!) y, float value) -> ()");
@@ -1184,6 +1213,7 @@ TORCH_LIBRARY_IMPL(s2v, CUDA, m) {
     m.impl("pad_reflect_", &pad_reflect_);
     m.impl("row_pack_", &row_pack_);
     m.impl("torgb_up2_", &torgb_up2_);
+    m.impl("tapsum_up2_", &tapsum_up2_);
     m.impl("flow_warp_", &flow_warp_);
     m.impl("flow_warp_cat_", &flow_warp_cat_);
     m.impl("fill_value_", &fill_value_);

@@ -66,6 +66,15 @@ RESUME_GRID = os.environ.get("S2V_ENET_RESUME_GRID", "")
 # cropped NCHW output itself.  Kept pixels are bit for bit those of the full-frame tail.  S2V_ENET_CROP_TAIL=0:
 # the full-frame tail
 CROP_TAIL = os.environ.get("S2V_ENET_CROP_TAIL", "1") == "1"
+# the x2-upsample StyleConv on >= 32 channels (StyleConv 3) as nine 1x1 tap products of the un-upsampled input and
+# one bilinear tap-sum pass (ops.tapsum_up2): conv3x3(up2(x)) = sum_t shift_t(up2(W_t x)), a quarter of the polyphase
+# form's multiply-adds and exact on every output line (no edge strips).  S2V_ENET_TAPSUM=0: the polyphase d2s conv
+TAPSUM = os.environ.get("S2V_ENET_TAPSUM", "1") == "1"
+# the split-precision tile of the tap-product 1x1 conv (conv_plan.cpp kX3Tiles index + 1): pinned, with one K split,
+# so the cropped (196^2) and the full-frame (200^2) tail run the same kernel instance and agree bit for bit
+# (512x128, the tile of the tail's other N = 128 StyleConvs: measured against 256x256, 256x128 and the smaller tiles
+# in profiles/ab_tapsum_styleconv.txt)
+TAP_TILE = int(os.environ.get("S2V_ENET_TAP_TILE", "9"))
 OUT_CROP = 8                 # ENet.py:139
 
 
@@ -126,7 +135,7 @@ def fold_up2_conv3(w: torch.Tensor) -> torch.Tensor:
 class StyleLayer:
     """One ModulatedConv2d (StyleConv or ToRGB)."""
 
-    def __init__(self, sd, p, device, demodulate, upsample, is_rgb):
+    def __init__(self, sd, p, device, demodulate, upsample, is_rgb, tapsum=False):
         m = p + "modulated_conv."
         w = sd[m + "weight"].float()[0]                      # [O, I, k, k]
         self.k = w.shape[-1]
@@ -148,6 +157,12 @@ class StyleLayer:
         if upsample and self.k == 3 and (self.cin % 32 == 0 or (POLY_UP4 and self.cin == 4)):
             self.conv4 = ConvW(fold_up2_conv3(w), bias.repeat(4), device, padding=1)
             self.wsq4 = self.wsq.repeat(4, 1).contiguous()
+        # the tap-product form (TAPSUM): row t * O + o of the 1x1 weights is W[o, :, dy, dx], t = 3 dy + dx; the
+        # demodulation d[b, o] covers the whole 3x3 filter, so the nine tap blocks share the layer's wsq
+        self.conv9 = self.wsq9 = None
+        if tapsum and self.conv4 is not None and self.cin % 32 == 0 and self.cout % 4 == 0:
+            self.conv9 = ConvW(w.permute(2, 3, 0, 1).reshape(9 * self.cout, self.cin, 1, 1), None, device)
+            self.wsq9 = self.wsq.repeat(9, 1).contiguous()
         self.rp = None                                       # row-packed form (ROWPACK0): packed channel count
         if ROWPACK0 and self.conv4 is None and not is_rgb and self.k == 3 and self.cin * self.k <= 32:
             self.conv.make_rowpack(device)
@@ -181,7 +196,7 @@ class ENetEngine:
         self.final_linear = ConvW(wl, sd["final_linear.bias"], dev)
         self.layers = []
         for i in range(2):
-            self.layers.append(StyleLayer(sd, f"style_convs.{2 * i}.", dev, True, True, False))
+            self.layers.append(StyleLayer(sd, f"style_convs.{2 * i}.", dev, True, True, False, tapsum=True))
             self.layers.append(StyleLayer(sd, f"style_convs.{2 * i + 1}.", dev, True, False, False))
             self.layers.append(StyleLayer(sd, f"to_rgbs.{i}.", dev, False, False, True))
         # all six modulation Linears consume the same style code -> one GEMM; each layer's segment
@@ -213,14 +228,19 @@ class ENetEngine:
 
     def _demod_table(self, poly):
         """The four StyleConvs' demodulations (base_blocks.py:492-494) as one ops.DemodRows table; a
-        polyphase layer contributes its four parity-class blocks (wsq4)."""
-        if poly not in self._demod:
-            ls = [(self.mod_offs[j], self.layers[j].wsq4 if poly and self.layers[j].conv4 is not None
-                   else self.layers[j].wsq) for j in (0, 1, 3, 4)]
+        polyphase layer contributes its four parity-class blocks (wsq4), a tap-product layer (TAPSUM) its nine
+        tap blocks (wsq9)."""
+        key = (poly, TAPSUM)
+        if key not in self._demod:
+            def rows(L):
+                if poly and TAPSUM and L.conv9 is not None:
+                    return L.wsq9
+                return L.wsq4 if poly and L.conv4 is not None else L.wsq
+            ls = [(self.mod_offs[j], rows(self.layers[j])) for j in (0, 1, 3, 4)]
             t = ops.DemodRows(ls, self.device)
             t.width = [w.shape[0] for _, w in ls]
-            self._demod[poly] = t
-        return self._demod[poly]
+            self._demod[key] = t
+        return self._demod[key]
 
     def _demods(self, ctx, s2):
         """[B, nrows] demodulation vectors of the four StyleConvs, one launch (instead of one per layer
@@ -243,7 +263,9 @@ class ENetEngine:
                 sv = s2[:, off: off + L.cin]
                 if L.cin <= 4:
                     continue      # the 4-channel first StyleConv runs exact fp32 (conv_k4.hip): modulated in-launch
-                if POLY_UP and L.conv4 is not None:
+                if POLY_UP and TAPSUM and L.conv9 is not None:
+                    wb[idx] = {"conv9": ops.modulate_weights(ctx, L.conv9, sv, dall[:, r0: r0 + wd], b)}
+                elif POLY_UP and L.conv4 is not None:
                     d4 = dall[:, r0: r0 + wd]
                     wb[idx] = {"conv4": ops.modulate_weights(ctx, L.conv4, sv, d4, b)}
                     if strips:
@@ -251,6 +273,26 @@ class ENetEngine:
                 elif L.rp is None:
                     wb[idx] = {"conv": ops.modulate_weights(ctx, L.conv, sv, dall[:, r0: r0 + L.cout], b)}
         return wb
+
+    def _tapsum_styleconv(self, ctx, L, x: NHWC, s, d9, premod, noise, y: NHWC, frame=None, origin=(0, 0),
+                          src_origin=(0, 0)):
+        """StyleConv(sample_mode='upsample') in the tap-product form (TAPSUM): the nine 1x1 products W_t x of the
+        un-upsampled ``x`` (one modulated 1x1 conv to 9 cout channels, plain epilogue), then ops.tapsum_up2: the
+        bilinear x2 samples of the nine planes at the taps' shifted positions summed, + noise + bias + LeakyReLU.
+        Exact on every output line of the frame: the clamped edge rows of the upsample and the conv's zero padding
+        are the tap-sum's own border cases.  ``x`` / ``y`` (and ``noise``) may be windows of their frames (``frame``
+        = x's, ``src_origin`` / ``origin`` as ops.tapsum_up2).  The 1x1 conv runs on one pinned tile with one K
+        split whatever the window's size (a 1x1 conv's output pixel depends on its input pixel alone), and the
+        tap-sum's order is fixed, so a pixel gets the same bits from a window as from the whole frame.  The products
+        are an fp32 [B, h, w, 9 cout] buffer: 2.83 GB per lane for ENet's B = 16 196^2 window, written once and
+        read once."""
+        # (band by band, a band's products consumed from the last-level cache, measured slower: DESIGN §8)
+        p = NHWC.empty(x.n, x.h, x.w, 9 * L.cout, self.device)
+        tile = TAP_TILE if ops.prec_code() != ops.PREC_F32 else 0
+        ops.modulated_conv2d(ctx, x, L.conv9, p, s, d9, premod=premod, force_tile=tile, force_splits=1)
+        ops.tapsum_up2(ctx, p, y, bias=L.conv.shift, pix_add=noise, pix_w=L.noise_w or 0.0, act=ops.ACT_LRELU,
+                       alpha=LRELU, frame=frame, origin=origin, src_origin=src_origin)
+        return y
 
     def _poly_styleconv(self, ctx, L, cur: NHWC, s, d4, idx, noises, ctr, wb=None):
         """StyleConv(sample_mode='upsample') (base_blocks.py:500-533): F.interpolate(x, 2, bilinear) then
@@ -278,6 +320,8 @@ class ENetEngine:
         y = NHWC.empty(b, h2, w2, L.cout, dev)
         kw = dict(act=ops.ACT_LRELU, alpha=LRELU, pix_w=L.noise_w or 0.0)
         wb = wb or {}
+        if TAPSUM and L.conv9 is not None:        # the tap-product form (d4 is then the nine tap blocks): no strips
+            return self._tapsum_styleconv(ctx, L, cur, s, d4, wb.get("conv9"), noise, y)
         ops.modulated_conv2d(ctx, cur, L.conv4, y, s, d4, pix_add=noise, d2s=True, premod=wb.get("conv4"), **kw)
         c = cur.c
         if STACK_STRIPS:
@@ -373,10 +417,15 @@ class ENetEngine:
         o3, n3 = win["conv3"]
         s, r0, wb = mod(3)
         y = NHWC.empty(b, n3, n3, L[3].cout, dev)
-        ops.modulated_conv2d(ctx, x, L[3].conv4, y, s, dall[:, r0: r0 + dtab.width[2]], d2s=True,
-                             pix_w=L[3].noise_w or 0.0,
-                             pix_add=self._noise_window(ctx, L[3], 2, b, f2, o3, n3, noises, ctr),
-                             premod=wb.get("conv4"), **kw)
+        nz3 = self._noise_window(ctx, L[3], 2, b, f2, o3, n3, noises, ctr)
+        if TAPSUM and L[3].conv9 is not None:
+            # every tap of output rows 6 .. 393 reads low-resolution rows 2 .. 197: StyleConv 2's window
+            o2 = win["conv2"][0]
+            self._tapsum_styleconv(ctx, L[3], x, s, dall[:, r0: r0 + dtab.width[2]], wb.get("conv9"), nz3, y,
+                                   frame=(f1, f1), origin=(o3, o3), src_origin=(o2, o2))
+        else:
+            ops.modulated_conv2d(ctx, x, L[3].conv4, y, s, dall[:, r0: r0 + dtab.width[2]], d2s=True,
+                                 pix_w=L[3].noise_w or 0.0, pix_add=nz3, premod=wb.get("conv4"), **kw)
         o4, n4 = win["conv4"]
         s, r0, wb = mod(4)
         z = NHWC.empty(b, n4, n4, L[4].cout, dev)

@@ -1149,6 +1149,37 @@ def torgb_up2(ctx: Ctx, x: NHWC, cw: "ConvW", s: torch.Tensor, skip: NHWC, y, *,
     return y
 
 
+def up2_tap_window(origin: int, size: int, frame: int):
+    """(first, count) of the low-resolution lines of a ``frame``-line axis that the 3x3 taps of upsampled output
+    lines [origin, origin + size) read: the bilinear (align_corners=False) sources of upsampled lines origin - 1 ..
+    origin + size inside the 2 frame-line output (tapsum_up2's host check, the same rule)."""
+    q0, q1 = max(origin - 1, 0), min(origin + size, 2 * frame - 1)
+    lo = int(max(0.5 * (q0 + 0.5) - 0.5, 0.0))
+    hi = min(int(max(0.5 * (q1 + 0.5) - 0.5, 0.0)) + 1, frame - 1)
+    return lo, hi - lo + 1
+
+
+def tapsum_up2(ctx: Ctx, p: NHWC, y: NHWC, *, bias=None, pix_add=None, pix_w=0.0, gain=1.0, act=ACT_NONE, alpha=0.0,
+               frame=None, origin=(0, 0), src_origin=(0, 0)):
+    """x2 bilinear upsample + 3x3 conv + noise + bias + activation from the nine 1x1 tap products of the
+    un-upsampled input (``s2v::tapsum_up2_``): p [B, h, w, 9 C] holds W_t x for the taps t = 3 dy + dx (tap-major),
+    y [B, 2h, 2w, C] = act(gain * sum_t up2(p_t) shifted by (dy - 1, dx - 1) + bias + pix_w * pix_add), zero where a
+    shifted position leaves the frame; pix_add [B, 2h, 2w] (y's shape).
+    ``frame`` = (h, w) of the low-resolution frame: p is its window at ``src_origin`` and y (and pix_add) the window
+    at ``origin`` of the (2h, 2w) output frame; the taps are the frame's and the sum's order is fixed, so a pixel gets
+    bit for bit the whole-frame value (the op refuses a window whose taps leave p)."""
+    assert p.n == y.n and p.c == 9 * y.c, "tapsum_up2: p carries nine tap blocks of y's channels"
+    if frame is None:
+        assert origin == (0, 0) and src_origin == (0, 0) and (y.h, y.w) == (2 * p.h, 2 * p.w)
+        window = []
+    else:
+        window = [int(frame[0]), int(frame[1]), int(origin[0]), int(origin[1]), int(src_origin[0]), int(src_origin[1])]
+    if pix_add is not None:
+        assert tuple(pix_add.shape) == (y.n, y.h, y.w) and pix_add.is_contiguous()
+    S2V.tapsum_up2_(p.v, pix_add, float(pix_w), bias, float(gain), int(act), float(alpha), y.v, window)
+    return y
+
+
 def row_pack(ctx: Ctx, x: NHWC, y: NHWC, kw: int, pw: int):
     """y[n, h, w, dx * c + ci] = x[n, h, w + dx - pw, ci] (zero outside the row and past kw * c)."""
     S2V.row_pack_(x.v, y.v, kw, pw)
