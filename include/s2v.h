@@ -710,6 +710,39 @@ int s2v_jpeg_decode(const uint8_t *data, long data_bytes, const int *intervals, 
                     long pitch_bytes, long frame_stride_bytes, int bgr, int *status, void *ws, long ws_bytes, int split,
                     s2v_stream_t stream);
 long s2v_jpeg_decode_ws_bytes(int n, int h, int w, int sampling);
+/* s2v_jpeg_decode with the entropy stage parallel inside an interval, for streams without restart markers (what
+ * Pillow and ffmpeg write): the same arguments with sub_bytes in place of split, the same pixels and the same status
+ * codes.  Huffman-coded data re-synchronises a decoder that starts at a wrong place, so an interval is cut into
+ * subsequences of sub_bytes raw (stuffed) bytes, a multiple of 4 from 4 to 4096, one lane each, one workgroup per
+ * interval:
+ *   state    at a cut: (position of the next unread bit, block within the MCU j, zigzag index k; k = 0: a DC code
+ *            is next).  Positions are canonical: behind the last bit of a data byte 0xFF lies the byte after its
+ *            stuffed 0x00, and a state on a stuffed 0x00 means the byte after it;
+ *   F        decodes symbols from a state while the next code starts before the subsequence's end, and returns the
+ *            exit state and a summary (blocks closed, DC differences summed per component, the first error and its
+ *            block).  A position at or past the end passes through.  F is total: where no code leads it skips one
+ *            bit, a DC category above 11 counts as difference 0, a run past 63 closes the block, and once a zero bit
+ *            from past the data is consumed it finishes the block on zero bits (as the serial decoder would) and
+ *            stops; the interval's last subsequence does the same at the interval's end.  These are noted as errors
+ *            1, 1, 2, 3 in the summary and nowhere else.  No byte outside the interval is read;
+ *   resolve  t[0] = (interval start, 0, 0) is true, t[b] starts as (b's first bit, 0, 0); t[b + 1] = F_b(t[b]) for
+ *            all b, round after round, until nothing changes: at most (subsequences + 1) rounds, which always
+ *            suffice since t[0..r] are true after round r.  The fixed point is the serial decoder's chain;
+ *   write    exclusive scans of the summaries give each subsequence its first block and DC predictors; one more F
+ *            from the true states writes the coefficients of the interval's count * blocks-per-MCU blocks into the
+ *            cleared workspace and decodes nothing after them (the padding bits raise no status);
+ *   status   of an interval: the error at the lowest block index below count * blocks-per-MCU, which is the serial
+ *            decoder's first error; of a frame: the largest of its intervals'.  4 also when the intervals table is
+ *            not in ascending order of offsets or two neighbours overlap (every frame gets it).
+ * ws >= s2v_jpeg_decode_sync_ws_bytes(...) bytes (0: bad arguments), 16-byte aligned: s2v_jpeg_decode's workspace and
+ * 48 bytes for each of data_bytes / sub_bytes + 2 n_intervals + 2 subsequence records.  Stream-ordered, no host
+ * synchronisation, no waiting between workgroups.  profiles/mjpeg_sync_micro.txt. */
+int s2v_jpeg_decode_sync(const uint8_t *data, long data_bytes, const int *intervals, int n_intervals,
+                         const int *frame_first, int max_per_frame, int n, int h, int w, int sampling,
+                         const uint16_t *qtables, const uint8_t *huff_sets, int n_sets, const int *set_index,
+                         uint8_t *out, long pitch_bytes, long frame_stride_bytes, int bgr, int *status, void *ws,
+                         long ws_bytes, int sub_bytes, s2v_stream_t stream);
+long s2v_jpeg_decode_sync_ws_bytes(int n, int h, int w, int sampling, long data_bytes, int n_intervals, int sub_bytes);
 /* cv2.warpAffine(src, M, (ow, oh), flags=INTER_LINEAR or INTER_AREA, BORDER_CONSTANT 0) on n HWC
  * images (dtype 0 uint8, 1 fp32, 2 fp64; pitches in elements): M = n device 2x3 fp64 forward
  * matrices, inverted on the device (invertAffineTransform); OpenCV's fixed-point source coordinates

@@ -162,6 +162,10 @@ _SIGS = {
                                  _c_int, _vp, _vp, ctypes.c_long, ctypes.c_long, _c_int, _vp, _vp, ctypes.c_long,
                                  _c_int, _vp]),
     "s2v_jpeg_decode_ws_bytes": (ctypes.c_long, [_c_int, _c_int, _c_int, _c_int]),
+    "s2v_jpeg_decode_sync": (_c_int, [_vp, ctypes.c_long, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                      _vp, _vp, _c_int, _vp, _vp, ctypes.c_long, ctypes.c_long, _c_int, _vp, _vp,
+                                      ctypes.c_long, _c_int, _vp]),
+    "s2v_jpeg_decode_sync_ws_bytes": (ctypes.c_long, [_c_int, _c_int, _c_int, _c_int, ctypes.c_long, _c_int, _c_int]),
     "s2v_bn_act_nhwc": (_c_int, [_vp, _c_ll, _c_int, _c_ll, _c_int, _vp, _vp, _vp, _c_ll, _c_int, _vp]),
     "s2v_fan_merge": (_c_int, [_vp, _c_ll, _vp, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_ll, _vp, _c_ll,
                                _vp, _vp, _vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp]),

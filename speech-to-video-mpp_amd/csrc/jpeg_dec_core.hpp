@@ -104,8 +104,9 @@ struct BitReader {
     S2V_JD bool ran_dry() const { return nbits < fake; }
 };
 
-// one symbol (call fill() first); -1: no code of up to 16 bits leads the stream
-S2V_JD int huff_decode(BitReader &br, const HuffTable &t) {
+// one symbol (call fill() first); -1: no code of up to 16 bits leads the stream.  Reader: BitReader or PosReader
+template <class Reader>
+S2V_JD int huff_decode(Reader &br, const HuffTable &t) {
     const unsigned v = br.peek(16);
     const unsigned e = t.look[v >> 8];
     if (e) {
@@ -212,6 +213,213 @@ S2V_JD int decode_interval(const EntropyArgs &a, const Interval &iv, const HuffT
     }
     return ST_OK;
 }
+
+// ----------------------------------------------------------------------------------------------------------------
+// The "sync" entropy decoder (s2v_jpeg_decode_sync): an interval is cut into subsequences of sub_bytes raw
+// (stuffed) bytes, the last one shorter, and subsequence b is decoded from the state its left neighbour hands it.
+//
+// A state is (pos, j, k): pos the position of the next unread bit, 8 * (byte index in the stream) + bit, j the
+// block within the MCU, k the zigzag index (0: a DC code comes next); packed pos << 16 | j << 8 | k.  Positions are
+// canonical: once the last bit of a data byte 0xFF is consumed the position is that of the byte after its stuffed
+// 0x00, and a state that points at a stuffed 0x00 is moved past it when it is opened.  Past the interval's end (or
+// past a marker inside it) the reader feeds zero bits, as BitReader does, and the position goes on counting them.
+constexpr int SYNC_SUB_MIN = 4, SYNC_SUB_MAX = 4096;
+constexpr int SYNC_RECORD_BYTES = 48;      // per subsequence: two state buffers, the last entry state, a summary
+
+S2V_JD unsigned long long sync_pack(long pos, int j, int k) {
+    return ((unsigned long long)pos << 16) | ((unsigned)j << 8) | (unsigned)k;
+}
+
+// what one subsequence, decoded from its entry state, adds to the interval
+struct SyncSummary {
+    int blocks;                    // blocks closed
+    int dc[3];                     // sum of the DC differences per component
+    int err, err_block;            // the first Status that is not ST_OK and the (local) block it lies in
+};
+
+// BitReader that knows where it is.  smask bit i: byte i of acc, counted from the low end, is a 0xFF whose stuffed
+// 0x00 was skipped; vpos: the next byte to load, counting on past the end of the data.
+struct PosReader {
+    const unsigned char *p;
+    long vpos, end;
+    unsigned long long acc;
+    int nbits, fake;
+    unsigned smask;
+    bool dead;
+
+    S2V_JD void open(const unsigned char *base, long off, long stop, long bitpos) {
+        p = base;
+        end = stop;
+        acc = 0;
+        nbits = 0;
+        fake = 0;
+        smask = 0;
+        long b = bitpos >> 3;
+        const int bit = (int)(bitpos & 7);
+        dead = b >= end;
+        if (!dead && bit == 0 && b > off && p[b - 1] == 0xFFu && p[b] == 0) ++b;   // a start on a stuffed 0x00
+        vpos = b;
+        fill();
+        skip(bit);
+    }
+    S2V_JD void fill() {
+        while (nbits <= 56) {
+            unsigned b = 0, st = 0;
+            if (!dead && vpos < end) {
+                b = p[vpos];
+                if (b == 0xFFu) {
+                    if (vpos + 1 < end && p[vpos + 1] == 0) {
+                        st = 1;
+                        ++vpos;
+                    } else {
+                        dead = true;       // a marker, or 0xFF as the last byte: the data ends
+                        b = 0;
+                    }
+                }
+            } else {
+                dead = true;
+            }
+            if (dead) fake += 8;
+            ++vpos;
+            acc = (acc << 8) | b;
+            smask = (smask << 1) | st;
+            nbits += 8;
+        }
+    }
+    S2V_JD unsigned peek(int n) const { return (unsigned)(acc >> (nbits - n)) & ((1u << n) - 1u); }
+    S2V_JD void skip(int n) { nbits -= n; }
+    S2V_JD bool ran_dry() const { return nbits < fake; }
+    // of the next unread bit, not of the read-ahead: a 0xFF with unread bits still has its 0x00 ahead of it
+    S2V_JD long position() const {
+        const int bytes = (nbits + 7) >> 3;
+        const int ahead = __builtin_popcount(smask & ((1u << bytes) - 1u));
+        return vpos * 8 - nbits - 8 * ahead;
+    }
+};
+
+// F: subsequence [sub_begin, sub_end) of the interval [off, end), entered in ``state`` -> the exit state.  Symbols
+// (a code and its extra bits) are decoded while the next one starts before sub_end; an entry position at or past
+// sub_end passes through unchanged.  F is total, and what is an error to the serial decoder is only noted in
+// ``sum`` and decoding goes on by a fixed rule:
+//   no code leads the 16 bits (ST_BAD_CODE)     one bit is skipped, j and k stay;
+//   a DC category above 11 (ST_BAD_CODE)        the code is consumed, the difference is 0, k = 1;
+//   a run past coefficient 63 (ST_RUN_PAST_63)  the code is consumed and the block closes;
+//   a zero bit from past the data is consumed   the block is finished on zero bits whatever sub_end is, the error
+//       is the first of the above that this meets, else ST_DATA_ENDS (ran_dry's rule: at the block's close), and
+//       F returns with the block closed, at max(position, sub_end).
+// The interval's last subsequence (sub_end == end) never passes through and finishes its block, or decodes one more,
+// on zero bits in the same way, so an interval that is short of blocks has the serial decoder's error.  An entry
+// state that no decoder can have produced (j, k out of range, a position before sub_begin) is read as (sub_begin, 0,
+// 0).  No byte outside [off, end) is read.  With dst (the interval's first coefficient) the non-zero coefficients
+// and the DC of blocks first_block + local index < total_blocks are written and decoding stops at total_blocks:
+// p0..p2 are the DC predictors on entry.
+S2V_JD unsigned long long sync_step(const unsigned char *stream, long off, long end, long sub_begin, long sub_end,
+                                    unsigned long long state, const HuffTable *tab, int hs, int vs, int bpm,
+                                    SyncSummary &sum, short *dst, long long first_block, long long total_blocks, int p0,
+                                    int p1, int p2) {
+    sum.blocks = 0;
+    sum.dc[0] = sum.dc[1] = sum.dc[2] = 0;
+    sum.err = ST_OK;
+    sum.err_block = 0;
+    long pos = (long)(state >> 16);
+    int j = (int)(state >> 8) & 255, k = (int)state & 255;
+    if (j >= bpm || k > 63 || pos < sub_begin * 8) {
+        pos = sub_begin * 8;
+        j = k = 0;
+    }
+    const long stop = sub_end * 8;
+    const bool last = sub_end >= end;
+    if (pos >= stop && !last) return sync_pack(pos, j, k);
+    PosReader br;
+    br.open(stream, off, end, pos);
+    unsigned d0 = 0, d1 = 0, d2 = 0;       // the DC differences summed per component: selects, no indexed array
+    bool dry = false;
+    for (;;) {
+        if (dst && (unsigned long long)(first_block + sum.blocks) >= (unsigned long long)total_blocks) break;
+        if (!dry && br.position() >= stop) {
+            if (!last) break;
+            dry = true;
+        }
+        br.fill();
+        const int c = block_component(j, hs, vs);
+        short *blk = dst ? dst + (first_block + sum.blocks) * 64 : nullptr;
+        int err = ST_OK;
+        bool close = false;
+        if (k == 0) {
+            const int s = huff_decode(br, tab[2 * c]);
+            if (s < 0) {
+                err = ST_BAD_CODE;
+                br.skip(1);
+            } else if (s > 11) {
+                err = ST_BAD_CODE;
+                k = 1;
+            } else {
+                int diff = 0;
+                if (s) {
+                    diff = huff_extend((int)br.peek(s), s);
+                    br.skip(s);
+                }
+                unsigned &d = c == 0 ? d0 : (c == 1 ? d1 : d2);
+                d += (unsigned)diff;
+                if (blk) blk[0] = (short)(int)((unsigned)(c == 0 ? p0 : (c == 1 ? p1 : p2)) + d);
+                k = 1;
+            }
+        } else {
+            const int rs = huff_decode(br, tab[2 * c + 1]);
+            if (rs < 0) {
+                err = ST_BAD_CODE;
+                br.skip(1);
+            } else {
+                const int r = rs >> 4, s = rs & 15;
+                if (s == 0) {
+                    if (r != 15) {
+                        close = true;      // EOB
+                    } else if (k + 16 > 63) {
+                        err = ST_RUN_PAST_63;
+                        close = true;
+                    } else {
+                        k += 16;
+                    }
+                } else if (k + r > 63) {
+                    err = ST_RUN_PAST_63;
+                    close = true;
+                } else {
+                    k += r;
+                    const int v = huff_extend((int)br.peek(s), s);
+                    br.skip(s);
+                    if (blk) blk[k] = (short)v;
+                    close = ++k == 64;
+                }
+            }
+        }
+        dry = dry || br.ran_dry();
+        if (dry && !err && close) err = ST_DATA_ENDS;
+        if (err && !sum.err) {
+            sum.err = err;
+            sum.err_block = sum.blocks;
+        }
+        if (close || (dry && err)) {
+            ++sum.blocks;
+            j = j + 1 == bpm ? 0 : j + 1;
+            k = 0;
+            if (dry) break;
+        }
+    }
+    sum.dc[0] = (int)d0;
+    sum.dc[1] = (int)d1;
+    sum.dc[2] = (int)d2;
+    const long at = br.position();
+    return sync_pack(at > stop ? at : stop, j, k);
+}
+
+// subsequences of an interval of ``len`` bytes: at least one, so that an empty interval still raises its status
+S2V_JD long sync_subs(long len, int sub_bytes) { return len > 0 ? (len + sub_bytes - 1) / sub_bytes : 1; }
+// records the workspace holds behind Dims::total; interval iv's lie at sync_base .. + sync_subs, apart from every
+// other interval's when the table is in ascending order and no two intervals overlap
+S2V_JD long sync_records(long data_bytes, int n_intervals, int sub_bytes) {
+    return data_bytes / sub_bytes + 2L * n_intervals + 2;
+}
+S2V_JD long sync_base(long off, int iv, int sub_bytes) { return off / sub_bytes + 2L * iv; }
 
 // jidctint's jpeg_idct_islow, one 1-D pass without its rounding shift, in 64-bit integers (libjpeg's JLONG)
 S2V_JD void idct_islow_pass(const long long *i, long long *o) {

@@ -203,13 +203,15 @@ def _frames(face: str, max_frames: int):
         f"synthetic {info['width']}x{info['height']} (no decoder; {info['frames']} frames in the file)"
 
 
-def decode_jpeg_frames(files, dev, batch: int = 16, first: int = 0) -> torch.Tensor:
+def decode_jpeg_frames(files, dev, batch: int = 16, first: int = 0, jpeg_decode: str | None = "wave") -> torch.Tensor:
     """JPEG files of one size and sampling -> uint8 BGR [n, H, W, 3] on ``dev``, decoded there in batches of
     ``batch`` (mjpeg.JpegDecoder): the frames never exist on the host.  A damaged stream raises ValueError naming
-    its frame (``first``: the number of files[0] in the clip)."""
+    its frame (``first``: the number of files[0] in the clip).  ``jpeg_decode``: the decoder's ``split``
+    (mjpeg.jpeg_decode_mode: "wave", "lane", "sync", "auto"; None reads S2V_JPEG_DECODE)."""
     from . import mjpeg
     info = mjpeg.parse_jpeg(files[0])
-    dec = mjpeg.JpegDecoder(info.h, info.w, info.sampling, order="bgr", device=dev)
+    dec = mjpeg.JpegDecoder(info.h, info.w, info.sampling, order="bgr", device=dev,
+                            split=mjpeg.jpeg_decode_mode(jpeg_decode))
     out = torch.empty((len(files), info.h, info.w, 3), dtype=torch.uint8, device=dev)
     status = []
     for s in range(0, len(files), max(1, batch)):
@@ -403,7 +405,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None,
         landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None,
         up_face: str = "original", without_rl1: bool = False, up_face_model=None, precision: str | None = None,
-        nms: str | None = "host", fps: float = 25.0):
+        nms: str | None = "host", fps: float = 25.0, jpeg_decode: str | None = "wave"):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -435,11 +437,15 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     ``face``: NAME.avi (Motion-JPEG: the frames are decoded on the device in batches of ``batch`` and stay there, fps
     from the header, ``meta["video"]`` "avi mjpeg WxH"; a damaged frame raises ValueError naming it), NAME.jpg /
     .jpeg (the reference's static mode: the one frame for every mel window up to ``max_frames``, at ``fps``), an MP4
-    (header only: synthetic frames) or an .npy array.  ``fps`` is used for a static image only."""
+    (header only: synthetic frames) or an .npy array.  ``fps`` is used for a static image only.  ``jpeg_decode``:
+    how the entropy stage of the JPEG decoder is split: "wave" (the default), "lane", "sync" (parallel inside an
+    interval: for files without restart markers, which is what ffmpeg and Pillow write), "auto" or None for
+    S2V_JPEG_DECODE; ``meta["jpeg_decode"]`` records it."""
     kw = dict(locals())                                     # the arguments (nothing else is bound yet)
-    from . import audio, ops, pipeline, post, synth
+    from . import audio, mjpeg, ops, pipeline, post, synth
     from . import face as faces
     nms = kw["nms"] = faces.nms_mode(nms)                   # ValueError on a bad name before anything runs
+    jpeg_decode = kw["jpeg_decode"] = mjpeg.jpeg_decode_mode(jpeg_decode)           # likewise
     if precision is not None:
         kw["precision"] = None
         with ops.precision(precision):                      # ValueError on a bad name before anything runs
@@ -466,11 +472,11 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     if kind == ".avi":
         if n == 0:
             raise ValueError(f"{face}: no frames")
-        frames = decode_jpeg_frames(reader.frames(0, n), dev, batch)
+        frames = decode_jpeg_frames(reader.frames(0, n), dev, batch, jpeg_decode=jpeg_decode)
         src_kind = f"avi mjpeg {frames.shape[2]}x{frames.shape[1]}"
     elif kind in (".jpg", ".jpeg"):
         with open(face, "rb") as f:
-            one = decode_jpeg_frames([f.read()], dev)
+            one = decode_jpeg_frames([f.read()], dev, jpeg_decode=jpeg_decode)
         frames = one.repeat(n, 1, 1, 1)                                             # one frame for every window
         src_kind = f"jpeg {one.shape[2]}x{one.shape[1]} (static)"
     else:
@@ -567,7 +573,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
             "mel_cols": int(mel.shape[1]), "mel_windows": int(chunks.shape[0]), "wav_samples_16k": int(len(wav)),
             "box": [y1, y2, x1, x2], "semantic": skind, "ref_enhance": ref_hook is not None,
             "restore": bool(enhance and restore), "up_face": up_face, "without_rl1": bool(without_rl1),
-            "up_face_weights": ukind, "conv_arith": ops.PRECISION, "nms": nms,
+            "up_face_weights": ukind, "conv_arith": ops.PRECISION, "nms": nms, "jpeg_decode": jpeg_decode,
             "seconds": round(time.time() - t0, 3)}
     if face_det:
         meta["boxes"] = [list(b) for b in boxes]
@@ -626,6 +632,10 @@ def build_parser():
     ap.add_argument("--nms", default=None, choices=["host", "device"],
                     help="where every detector's greedy NMS runs (default: S2V_NMS, else host); device: the "
                          "batched kernel, equal scores take the larger position index first")
+    ap.add_argument("--jpeg_decode", default=None, choices=["wave", "lane", "sync", "auto"],
+                    help="with --face NAME.avi / .jpg: the split of the JPEG decoder's entropy stage (default: "
+                         "S2V_JPEG_DECODE, else wave); sync decodes inside a restart interval in parallel, for files "
+                         "without restart markers (ffmpeg's and Pillow's); auto picks sync for long intervals")
     ap.add_argument("--jpeg_quality", type=int, default=95,
                     help="with --outfile NAME.avi: JPEG quality 1..100 (the reference asks ffmpeg for its best, -q:v 1)")
     return ap
@@ -655,7 +665,7 @@ def main(argv=None):
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
             nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
             stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1, precision=a.precision,
-            nms=a.nms, fps=a.fps)
+            nms=a.nms, fps=a.fps, jpeg_decode=a.jpeg_decode)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     if a.outfile.lower().endswith(".avi"):
         video = r["enhanced"] if r["enhanced"] is not None else r["frames"]

@@ -9,11 +9,13 @@ interval per MCU row.  ``jfif_header`` writes everything up to the entropy-coded
 The decoder takes any baseline stream ``parse_jpeg`` accepts -- SOF0, 8 bit, YCbCr at 4:4:4, 4:2:2
 or 4:2:0, one interleaved scan, any tables, any restart interval -- and gives libjpeg's pixels bit for bit.  Its unit
 of parallel work is the restart interval: a stream without restart markers (Pillow's and ffmpeg's default) is decoded
-by one lane per frame, correct and slow.  ``ffmpeg -i in.mp4 -c:v mjpeg -q:v 2 out.avi`` makes a file ``AviReader``
-reads.  There is no MP4 and no other codec: a user with ffmpeg transcodes.
+by one lane per frame, correct and slow, unless the opt-in ``split="sync"`` (s2v_jpeg_decode_sync) decodes inside the
+interval in parallel.  ``ffmpeg -i in.mp4 -c:v mjpeg -q:v 2 out.avi`` makes a file ``AviReader`` reads.  There is no
+MP4 and no other codec: a user with ffmpeg transcodes.
 """
 from __future__ import annotations
 
+import os
 import struct
 import wave
 from dataclasses import dataclass
@@ -366,15 +368,46 @@ def pack_streams(files, h: int, w: int, sampling: int):
     for k, v in parts.items():
         buf[offs[k]:offs[k] + v.nbytes] = np.ascontiguousarray(v).view(np.uint8).reshape(-1)
     counts = {"n": len(files), "intervals": int(first[-1]), "max_per_frame": int(np.diff(first).max()),
-              "sets": len(sets), "data_bytes": base}
+              "sets": len(sets), "data_bytes": base, "max_interval_bytes": int(parts["intervals"][:, 1].max())}
     return buf, offs, counts
+
+
+JPEG_DECODE_ENV = "S2V_JPEG_DECODE"
+JPEG_DECODE_MODES = ("wave", "lane", "sync", "auto")       # the entropy stage's split (JpegDecoder)
+# Set from profiles/mjpeg_sync_micro.txt (tools/mjpeg_decode_micro.py --sync on an MI355X, 16 frames).
+# SYNC_SUB_BYTES: of the sweep 64 .. 2048, 256 is the fastest on Pillow's 700x700 streams and within a quarter of
+# the fastest (1024) at 1400x1400.  SYNC_AUTO_BYTES: "auto" takes sync when the batch's
+# longest interval has more bytes than this.  In the crossover rows sync passes wave between 2.3 and 4.7 KB an interval
+# and is 4 times faster at 17 KB; the project's own streams at 1400x1400 have intervals of 10 KB, 88 a frame, where
+# sync at 256 bytes is no faster than wave: the threshold lies above them.
+SYNC_SUB_BYTES = 256
+SYNC_AUTO_BYTES = 16384
+
+
+def jpeg_decode_mode(mode="wave") -> str:
+    """A ``jpeg_decode=`` / ``split=`` name: one of JPEG_DECODE_MODES (0 and 1 are "wave" and "lane"); None reads
+    S2V_JPEG_DECODE (unset or empty: "wave").  Anything else raises ValueError."""
+    source = "jpeg_decode="
+    if mode is None:
+        mode, source = os.environ.get(JPEG_DECODE_ENV) or "wave", JPEG_DECODE_ENV + "="
+    if mode in (0, 1) and not isinstance(mode, bool):
+        mode = JPEG_DECODE_MODES[mode]
+    if mode not in JPEG_DECODE_MODES:
+        raise ValueError(f"{source}{mode!r}: {JPEG_DECODE_ENV} / jpeg_decode= takes one of "
+                         f"{', '.join(JPEG_DECODE_MODES)}")
+    return mode
 
 
 class JpegDecoder:
     """Baseline JPEG files of one size and sampling -> uint8 [n, h, w, 3] device frames, one launch sequence and
-    one host -> device copy per batch.  ``split``: 0 one wave per restart interval, 1 one lane."""
+    one host -> device copy per batch.  ``split``, the entropy stage: 0 / "wave" one wave per restart interval, 1 /
+    "lane" one lane, "sync" one lane per ``sub_bytes`` (a multiple of 4 from 4 to 4096; None: SYNC_SUB_BYTES) of every
+    interval (s2v_jpeg_decode_sync: for streams without restart markers), "auto" sync when the batch's longest
+    interval exceeds SYNC_AUTO_BYTES, else wave.  Any other ``split`` (2, say) raises ValueError here, no longer in
+    s2v_jpeg_decode at the first batch.  ``picked``: the split the last batch ran with."""
 
-    def __init__(self, h: int, w: int, sampling: int = 2, order: str = "bgr", device="cuda", split: int = 0):
+    def __init__(self, h: int, w: int, sampling: int = 2, order: str = "bgr", device="cuda", split=0,
+                 sub_bytes: int | None = None):
         import torch
 
         from . import _lib
@@ -382,7 +415,13 @@ class JpegDecoder:
             raise ValueError(f"channel order {order!r}: 'bgr' or 'rgb'")
         if sampling not in (0, 1, 2):
             raise ValueError(f"sampling {sampling!r}: 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)")
-        self.h, self.w, self.sampling, self.order, self.split = int(h), int(w), int(sampling), order, int(split)
+        self.mode = jpeg_decode_mode(split)
+        self.split = split if isinstance(split, str) else int(split)
+        self.sub_bytes = SYNC_SUB_BYTES if sub_bytes is None else int(sub_bytes)
+        if not (4 <= self.sub_bytes <= 4096 and self.sub_bytes % 4 == 0):
+            raise ValueError(f"sub_bytes {sub_bytes!r}: a multiple of 4 from 4 to 4096")
+        self.picked = None
+        self.h, self.w, self.sampling, self.order = int(h), int(w), int(sampling), order
         self.device = torch.device(device)
         self.lib = _lib.load()
         self._ws = None
@@ -393,12 +432,13 @@ class JpegDecoder:
         info = parse_jpeg(data)
         return cls(info.h, info.w, info.sampling, **kw)
 
-    def _workspace(self, n: int):
+    def _workspace(self, n: int, nbytes: int = 0):
         import torch
-        if self._ws is None or self._ws_n < n:
-            nbytes = int(self.lib.s2v_jpeg_decode_ws_bytes(n, self.h, self.w, self.sampling))
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws_n = n
+        nbytes = nbytes or int(self.lib.s2v_jpeg_decode_ws_bytes(n, self.h, self.w, self.sampling))
+        if self._ws is None or self._ws_n < n or self._ws.numel() < nbytes:
+            self._ws = torch.empty(max(nbytes, 0 if self._ws is None else self._ws.numel()), dtype=torch.uint8,
+                                   device=self.device)
+            self._ws_n = max(n, self._ws_n)
         return self._ws
 
     def decode(self, files, out=None):
@@ -425,12 +465,27 @@ class JpegDecoder:
             raise ValueError(f"out strides {out.stride()}: channel stride 1, pixel stride 3, rows and frames apart")
         p = dev.data_ptr()
         status = torch.empty((n,), dtype=torch.int32, device=self.device)
+        mode = self.mode
+        if mode == "auto":                                 # from pack_streams' count: the table is not read back
+            mode = "sync" if cnt["max_interval_bytes"] > SYNC_AUTO_BYTES else "wave"
+        self.picked = mode
+        if mode == "sync":
+            need = int(self.lib.s2v_jpeg_decode_sync_ws_bytes(n, self.h, self.w, self.sampling, cnt["data_bytes"],
+                                                              cnt["intervals"], self.sub_bytes))
+            ws = self._workspace(n, need)
+            check(self.lib.s2v_jpeg_decode_sync(
+                p + offs["data"], cnt["data_bytes"], p + offs["intervals"], cnt["intervals"], p + offs["frame_first"],
+                cnt["max_per_frame"], n, self.h, self.w, self.sampling, p + offs["qtables"], p + offs["huff_sets"],
+                cnt["sets"], p + offs["set_index"], out.data_ptr(), sy, sn if n > 1 else 0,
+                1 if self.order == "bgr" else 0, status.data_ptr(), ws.data_ptr(), ws.numel(), self.sub_bytes,
+                torch.cuda.current_stream(self.device).cuda_stream), "s2v_jpeg_decode_sync")
+            return out, status
         ws = self._workspace(n)
         check(self.lib.s2v_jpeg_decode(p + offs["data"], cnt["data_bytes"], p + offs["intervals"], cnt["intervals"],
                                        p + offs["frame_first"], cnt["max_per_frame"], n, self.h, self.w, self.sampling,
                                        p + offs["qtables"], p + offs["huff_sets"], cnt["sets"], p + offs["set_index"],
                                        out.data_ptr(), sy, sn if n > 1 else 0, 1 if self.order == "bgr" else 0,
-                                       status.data_ptr(), ws.data_ptr(), ws.numel(), self.split,
+                                       status.data_ptr(), ws.data_ptr(), ws.numel(), JPEG_DECODE_MODES.index(mode),
                                        torch.cuda.current_stream(self.device).cuda_stream), "s2v_jpeg_decode")
         return out, status
 
