@@ -395,6 +395,29 @@ int s2v_melspectrogram(const float *wav, long long n_samples, const float *table
 int s2v_mel_chunks(const float *mel, long long frames, const int *starts, int nchunks, int step, float *out,
                    s2v_stream_t stream);
 
+/* sample formats of s2v_audio_load: interleaved little-endian, as a RIFF/WAVE data chunk holds them */
+enum {
+    S2V_PCM_U8 = 0,  /* (v - 128) / 128 */
+    S2V_PCM_S16 = 1, /* v / 2^15 */
+    S2V_PCM_S24 = 2, /* three bytes, sign-extended, v / 2^23 */
+    S2V_PCM_S32 = 3, /* (float)v (round to nearest), then / 2^31 */
+    S2V_PCM_F32 = 4, /* as it is */
+    S2V_PCM_F64 = 5  /* rounded to float32 */
+};
+
+/* Audio loader (librosa.load(path, sr) of futils/audio.py:10-11 after the file has been read): decode
+ * ``n_frames`` interleaved frames of ``channels`` samples at ``pcm`` (device bytes, any alignment the
+ * format's sample size divides), downmix (sequential fp32 sum over the channels in order, then an IEEE
+ * division by (float)channels: numpy's mean(axis=1) bit for bit) and resample by up/down with a
+ * phase-major filter table [up][row_stride] (row_stride >= 2 half, a multiple of 4, 16-byte aligned base):
+ *   out[k] = sum_{t = -half+1 .. half} x[floor(k down / up) + t] * table[k mod up][t + half - 1]
+ * x zero outside [0, n_frames); fp32 FMA, taps ascending from 0.0f, so out[k] depends on nothing but its
+ * own taps (not on the tile, the launch geometry or further samples).  n_out must be
+ * ceil(n_frames * up / down).  up == down: table may be null, half / row_stride are ignored and the call
+ * is a decode + downmix pass (n_out == n_frames).  n_frames == 0 launches nothing. */
+int s2v_audio_load(const void *pcm, long long n_frames, int channels, int format, const float *table, int up,
+                   int down, int half, int row_stride, float *out, long long n_out, s2v_stream_t stream);
+
 /* GPEN native ops, same signatures/semantics as third_part/GPEN/face_model/op/:
  *   fused_bias_act (fused_bias_act.cpp:4-21, fused_bias_act_kernel.cu:18-99)
  *   y = scale * act(x + b[(i / step_b) % C]) with act 1 = linear, 3 = leaky relu(alpha);

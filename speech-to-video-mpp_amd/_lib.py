@@ -17,6 +17,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_TANH, ACT_GELU_TANH = range(6)
 IN_DIRECT, IN_NEAREST_UP2, IN_TRANSPOSED = range(3)
 PAD_ZERO, PAD_REFLECT = range(2)
 PREC_F32, PREC_BF16X3, PREC_F16X3, PREC_F16 = range(4)
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)
 
 _c_int, _c_float, _c_ll, _c_size, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_void_p
 
@@ -95,6 +96,7 @@ _SIGS = {
                                    _c_ll, _c_ll, _vp, _c_int, _vp]),
     "s2v_melspectrogram": (_c_int, [_vp, _c_ll, _vp, _c_int, _vp, _c_ll, _vp]),
     "s2v_mel_chunks": (_c_int, [_vp, _c_ll, _vp, _c_int, _c_int, _vp, _vp]),
+    "s2v_audio_load": (_c_int, [_vp, _c_ll, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_ll, _vp]),
     "s2v_fused_bias_act": (_c_int, [_vp, _vp, _vp, _vp, _c_ll, _c_int, _c_ll, _c_int, _c_int, _c_float, _c_float,
                                     _vp]),
     "s2v_upfirdn2d": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,

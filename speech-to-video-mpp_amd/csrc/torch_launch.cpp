@@ -1122,6 +1122,35 @@ void melspectrogram_(const Tensor &wav, const Tensor &tables, bool pad_reflect, 
           "s2v_melspectrogram");
 }
 
+// pcm: the interleaved sample bytes as they lie in the file (uint8, device); table: [up, row_stride] or none
+// when up == down; out: [ceil(n_frames up / down)]
+void audio_load_(const Tensor &pcm, int64_t n_frames, int64_t channels, int64_t format, const OptT &table, int64_t up,
+                 int64_t down, int64_t half, const Tensor &out) {
+    const c10::DeviceGuard guard(out.device());
+    const at::Device dev = out.device();
+    f32(out, dev, "audio_load out");
+    same_dev(pcm, dev, "audio_load pcm");
+    static const int64_t kBytes[] = {1, 2, 3, 4, 4, 8};
+    TORCH_CHECK(format >= 0 && format < 6, "audio_load: unknown sample format ", format);
+    TORCH_CHECK(n_frames >= 0 && channels >= 1 && channels < (1 << 16), "audio_load: bad frame or channel count");
+    TORCH_CHECK(pcm.scalar_type() == at::kByte && pcm.dim() == 1 && pcm.is_contiguous() &&
+                    pcm.numel() / (kBytes[format] * channels) >= n_frames,
+                "audio_load: pcm must be contiguous uint8 holding n_frames * channels samples");
+    TORCH_CHECK(out.dim() == 1 && out.is_contiguous(), "audio_load: out [n_out]");
+    TORCH_CHECK(up >= 1 && down >= 1 && up < (1LL << 31) && down < (1LL << 31) && half >= 0 && half < (1 << 24),
+                "audio_load: bad up / down / half");
+    int64_t row_stride = 0;
+    const float *tab = nullptr;
+    if (up != down) {
+        TORCH_CHECK(has(table) && table->dim() == 2 && table->size(0) == up, "audio_load: table [up, row_stride]");
+        row_stride = table->size(1);
+        tab = vec(table, dev, up * row_stride, "audio_load table");
+    }
+    check(s2v_audio_load(pcm.data_ptr<uint8_t>(), n_frames, (int)channels, (int)format, tab, (int)up, (int)down,
+                         (int)half, (int)row_stride, out.data_ptr<float>(), out.size(0), stream()),
+          "s2v_audio_load");
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(s2v, m) {
@@ -1192,6 +1221,8 @@ TORCH_LIBRARY_FRAGMENT(s2v, m) {
     m.def("to_u8_(Tensor x, Tensor(a!) y, float lo, float hi, float scale, float offset) -> ()");
     m.def("mel_chunks_(Tensor mel, Tensor starts, int step, Tensor(a!) out) -> ()");
     m.def("melspectrogram_(Tensor wav, Tensor tables, bool pad_reflect, Tensor(a!) out) -> ()");
+    m.def("audio_load_(Tensor pcm, int n_frames, int channels, int format, Tensor? table, int up, int down, int half, "
+          "Tensor(a!) out) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(s2v, CUDA, m) {
@@ -1230,4 +1261,5 @@ TORCH_LIBRARY_IMPL(s2v, CUDA, m) {
     m.impl("to_u8_", &to_u8_);
     m.impl("mel_chunks_", &mel_chunks_);
     m.impl("melspectrogram_", &melspectrogram_);
+    m.impl("audio_load_", &audio_load_);
 }

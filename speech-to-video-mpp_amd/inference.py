@@ -6,7 +6,8 @@ examples/audio/1.wav, 8 frames, plumbing).
 
 Steps (reference file:line in brackets):
   * audio: stdlib ``wave`` PCM -> float32, channels averaged, resampled to 16 kHz
-    (audio.load_wav = librosa.load(path, sr=16000), futils/audio.py:10-11) -> mel on the device ->
+    (audio.load_wav = librosa.load(path, sr=16000), futils/audio.py:10-11), or with --audio_load device the same
+    three steps in one kernel on the file's sample bytes (s2v_amd.audio.load_audio) -> mel on the device ->
     16-column windows at 80 / fps columns per frame [inference.py:204-216];
   * video: --face NAME.avi is a Motion-JPEG AVI (``ffmpeg -i in.mp4 -c:v mjpeg -q:v 2 out.avi``): s2v_amd.mjpeg
     reads the container and decodes the frames on the device (JpegDecoder, batches of --LNet_batch_size), fps from
@@ -405,7 +406,8 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         pads=(0, 20, 0, 0), nosmooth: bool = False, face_det_batch_size: int = 4, detector=None,
         landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None,
         up_face: str = "original", without_rl1: bool = False, up_face_model=None, precision: str | None = None,
-        nms: str | None = "host", fps: float = 25.0, jpeg_decode: str | None = "wave"):
+        nms: str | None = "host", fps: float = 25.0, jpeg_decode: str | None = "wave",
+        audio_load: str | None = "host"):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -440,12 +442,16 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     (header only: synthetic frames) or an .npy array.  ``fps`` is used for a static image only.  ``jpeg_decode``:
     how the entropy stage of the JPEG decoder is split: "wave" (the default), "lane", "sync" (parallel inside an
     interval: for files without restart markers, which is what ffmpeg and Pillow write), "auto" or None for
-    S2V_JPEG_DECODE; ``meta["jpeg_decode"]`` records it."""
+    S2V_JPEG_DECODE; ``meta["jpeg_decode"]`` records it.  ``audio_load``: where ``audio_path`` becomes float32 mono
+    at 16 kHz: "host" (the default: load_wav, stdlib ``wave`` + NumPy), "device" (audio.load_audio: the file's sample
+    bytes are decoded, downmixed and resampled in one launch; it also reads IEEE-float and EXTENSIBLE files, which
+    ``wave`` refuses) or None for S2V_AUDIO_LOAD; ``meta["audio_load"]`` records it."""
     kw = dict(locals())                                     # the arguments (nothing else is bound yet)
     from . import audio, mjpeg, ops, pipeline, post, synth
     from . import face as faces
     nms = kw["nms"] = faces.nms_mode(nms)                   # ValueError on a bad name before anything runs
     jpeg_decode = kw["jpeg_decode"] = mjpeg.jpeg_decode_mode(jpeg_decode)           # likewise
+    audio_load = kw["audio_load"] = audio.audio_load_mode(audio_load)               # likewise
     if precision is not None:
         kw["precision"] = None
         with ops.precision(precision):                      # ValueError on a bad name before anything runs
@@ -465,8 +471,12 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     else:
         frames_np, fps, src_kind = _frames(face, max_frames)
         available = len(frames_np)
-    wav = load_wav(audio_path, 16000)
-    mel = audio.melspectrogram(torch.from_numpy(wav).to(dev))
+    if audio_load == "device":
+        wav = audio.load_audio(audio_path, 16000, dev)
+        mel = audio.melspectrogram(wav)
+    else:
+        wav = load_wav(audio_path, 16000)
+        mel = audio.melspectrogram(torch.from_numpy(wav).to(dev))
     chunks = audio.mel_chunks(mel, fps=fps)
     n = min(available, chunks.shape[0])                                             # inference.py:219-221
     if kind == ".avi":
@@ -574,6 +584,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
             "box": [y1, y2, x1, x2], "semantic": skind, "ref_enhance": ref_hook is not None,
             "restore": bool(enhance and restore), "up_face": up_face, "without_rl1": bool(without_rl1),
             "up_face_weights": ukind, "conv_arith": ops.PRECISION, "nms": nms, "jpeg_decode": jpeg_decode,
+            "audio_load": audio_load,
             "seconds": round(time.time() - t0, 3)}
     if face_det:
         meta["boxes"] = [list(b) for b in boxes]
@@ -597,7 +608,10 @@ def build_parser():
                     help="Motion-JPEG .avi (decoded on the device), one .jpg / .jpeg (static: the frame repeats), MP4 "
                          "(header read; synthetic frames) or uint8 [N,H,W,3] .npy")
     ap.add_argument("--fps", type=float, default=25.0, help="with --face NAME.jpg: frames per second of the clip")
-    ap.add_argument("--audio", required=True, help="PCM .wav")
+    ap.add_argument("--audio", required=True,
+                    help="PCM .wav (8/16/24/32 bit); with --audio_load device also IEEE-float (32/64 bit) and "
+                         "WAVE_FORMAT_EXTENSIBLE files; any rate and channel count: averaged to mono, resampled to "
+                         "16 kHz")
     ap.add_argument("--outfile", default="results/inference_frames.npz",
                     help="NAME.avi: a Motion-JPEG AVI of the frames (the --enhance output when there is one) with the "
                          "audio of --audio; anything else: the uint8 arrays as a compressed .npz")
@@ -636,19 +650,26 @@ def build_parser():
                     help="with --face NAME.avi / .jpg: the split of the JPEG decoder's entropy stage (default: "
                          "S2V_JPEG_DECODE, else wave); sync decodes inside a restart interval in parallel, for files "
                          "without restart markers (ffmpeg's and Pillow's); auto picks sync for long intervals")
+    ap.add_argument("--audio_load", default=None, choices=["host", "device"],
+                    help="where --audio is decoded, downmixed and resampled to 16 kHz (default: S2V_AUDIO_LOAD, else "
+                         "host); device: one kernel launch on the file's sample bytes")
     ap.add_argument("--jpeg_quality", type=int, default=95,
                     help="with --outfile NAME.avi: JPEG quality 1..100 (the reference asks ffmpeg for its best, -q:v 1)")
     return ap
 
 
-def write_avi(path: str, frames: torch.Tensor, fps: float, audio_path: str, quality: int = 95, batch: int = 16) -> int:
+def write_avi(path: str, frames: torch.Tensor, fps: float, audio_path: str, quality: int = 95, batch: int = 16,
+              audio_load: str | None = "host") -> int:
     """The reference's cv2.VideoWriter + ffmpeg mux (inference.py:246-249, :325-336) as one Motion-JPEG AVI:
     uint8 BGR [n, H, W, 3] device frames through mjpeg.JpegEncoder in batches of ``batch``, with the PCM of
-    ``audio_path`` at its own rate and channel count, cut to the clip.  -> the file's size in bytes."""
-    from . import mjpeg
+    ``audio_path`` at its own rate and channel count, cut to the clip.  ``audio_load`` "device" (None: S2V_AUDIO_LOAD)
+    takes the PCM from audio.pcm16, which also converts the float files load_audio reads; "host" from
+    mjpeg.wav_pcm16.  -> the file's size in bytes."""
+    from . import audio, mjpeg
+    pcm = audio.pcm16(audio_path) if audio.audio_load_mode(audio_load) == "device" else mjpeg.wav_pcm16(audio_path)
     n, H, W = frames.shape[:3]
     enc = mjpeg.JpegEncoder(H, W, quality=quality, order="bgr", device=frames.device)
-    with mjpeg.AviWriter(path, W, H, fps, audio=mjpeg.wav_pcm16(audio_path)) as avi:
+    with mjpeg.AviWriter(path, W, H, fps, audio=pcm) as avi:
         for s in range(0, n, max(1, batch)):
             for data in enc.encode_to_host(frames[s:s + max(1, batch)]):
                 avi.write(data)
@@ -665,11 +686,12 @@ def main(argv=None):
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
             nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
             stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1, precision=a.precision,
-            nms=a.nms, fps=a.fps, jpeg_decode=a.jpeg_decode)
+            nms=a.nms, fps=a.fps, jpeg_decode=a.jpeg_decode, audio_load=a.audio_load)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     if a.outfile.lower().endswith(".avi"):
         video = r["enhanced"] if r["enhanced"] is not None else r["frames"]
-        size = write_avi(a.outfile, video, r["meta"]["fps"], a.audio, a.jpeg_quality, a.LNet_batch_size)
+        size = write_avi(a.outfile, video, r["meta"]["fps"], a.audio, a.jpeg_quality, a.LNet_batch_size,
+                         audio_load=r["meta"]["audio_load"])
         print(json.dumps(dict(r["meta"], outfile=a.outfile, video_bytes=size, jpeg_quality=a.jpeg_quality)))
         return 0
     arrays = {"frames": r["frames"].cpu().numpy(), "preds": r["preds"].cpu().numpy()}

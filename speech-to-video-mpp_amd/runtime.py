@@ -3,7 +3,28 @@ replay), the MI355X replacement for a tracing compiler, and lanes of captured fo
 concurrently on their own streams."""
 from __future__ import annotations
 
+import contextlib
+import gc
+
 import torch
+
+
+@contextlib.contextmanager
+def capture_gc():
+    """Around a stream capture: collect dead reference cycles first and keep the automatic collector off until the
+    capture has ended.  A captured runner that died inside a cycle (LipSyncPipeline holds its LaneRunner, whose
+    function holds the pipeline) is freed only by the collector, and on ROCm torch's CUDAGraph destructor
+    synchronises the device, which is not allowed while a stream captures: the error is raised inside a destructor
+    and the process aborts.  torch.cuda.graph no longer collects on entry (torch.compiler.config.force_cudagraph_gc),
+    and whether a collection falls into a capture depends on the allocation count of everything that ran before."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class GraphRunner:
@@ -21,7 +42,7 @@ class GraphRunner:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with capture_gc(), torch.cuda.graph(self.graph):
             self.static_out = fn(*self.static_in)
         torch.cuda.synchronize()
 
