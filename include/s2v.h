@@ -245,7 +245,8 @@ int s2v_split_act(const float *x, long long pixels, int c, int xcs, int prec, fl
                   s2v_stream_t stream);
 
 /* LayerNorm2d (base_blocks.py:52-69) over (H,W,C) per sample, fused affine + act
- * (+ 2x2 average pool: DownBlock2d base_blocks.py:95-109) (+ residual after act: Jump + out,
+ * (+ 2x2 average pool: DownBlock2d base_blocks.py:95-109; y and res are [n][h / 2][w / 2], the last
+ * row / column of an odd image is dropped as F.avg_pool2d drops it) (+ residual after act: Jump + out,
  * LNet.py:75).  ws: >= s2v_layernorm2d_ws_bytes(n, h, w, c) bytes. */
 int s2v_layernorm2d(const float *x, int n, int h, int w, int c, int xcs,
                     const float *weight, const float *bias, float eps, int act, float alpha, int pool,
@@ -261,7 +262,8 @@ int s2v_instnorm_adain(const float *x, int n, int h, int w, int c, int xcs,
                        s2v_stream_t stream);
 /* s2v_instnorm_adain that also writes F.pad(y, (1, 1, 1, 1), 'reflect') to yp ([n][h+2][w+2],
  * pitch ypcs): the FFC's reflect-padded 3x3 convs read the next block's input without a separate
- * pad pass.  Vector path only (c % 4 == 0, 4-aligned pitches, 16-byte aligned x / y / yp / res). */
+ * pad pass.  Any h, w >= 2 (a 3-row / 3-column plane mirrors its middle line onto both borders).
+ * Vector path only (c % 4 == 0, 4-aligned pitches, 16-byte aligned x / y / yp / res). */
 int s2v_instnorm_adain_pad(const float *x, int n, int h, int w, int c, int xcs, const float *gamma,
                            const float *beta, int gb_ns, float eps, int act, float alpha, const float *res, int res_cs,
                            float *y, int ycs, float *yp, int ypcs, void *ws, size_t ws_bytes, s2v_stream_t stream);

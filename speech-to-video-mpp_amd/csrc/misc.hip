@@ -15,6 +15,16 @@ __device__ __forceinline__ void bilin_index(float scale, int dst, int in, int &i
     l0 = 1.f - l1;
 }
 
+// The four-tap sum ly0 * (lx0 a + lx1 b) + ly1 * (lx0 c + lx1 d) with its three roundings-by-fma written
+// out.  Left to the compiler, the contraction of the plain expression differed between the kernels and
+// between the channels of one float4 (the packed-math form pairs the products the other way round), so
+// the x2 kernel was the generic kernel's only to an ulp; every bilinear kernel below goes through here.
+__device__ __forceinline__ float bilin_sum(float ly0, float ly1, float lx0, float lx1, float a, float b, float c,
+                                           float d) {
+    const float top = fmaf(lx0, a, lx1 * b), bot = fmaf(lx0, c, lx1 * d);
+    return fmaf(ly0, top, ly1 * bot);
+}
+
 __global__ __launch_bounds__(256) void resize_kernel(const float *__restrict__ x, int n, int c, int ih, int iw,
                                                      long long xsn, long long xsc, long long xsy, long long xsx,
                                                      float *__restrict__ y, int oh, int ow, long long ysn,
@@ -35,8 +45,8 @@ __global__ __launch_bounds__(256) void resize_kernel(const float *__restrict__ x
             float ly0, ly1, lx0, lx1;
             bilin_index(sh, oy, ih, y0, y1, ly0, ly1);
             bilin_index(sw, ox, iw, x0, x1, lx0, lx1);
-            v = ly0 * (lx0 * xb[y0 * xsy + x0 * xsx] + lx1 * xb[y0 * xsy + x1 * xsx]) +
-                ly1 * (lx0 * xb[y1 * xsy + x0 * xsx] + lx1 * xb[y1 * xsy + x1 * xsx]);
+            v = bilin_sum(ly0, ly1, lx0, lx1, xb[y0 * xsy + x0 * xsx], xb[y0 * xsy + x1 * xsx],
+                          xb[y1 * xsy + x0 * xsx], xb[y1 * xsy + x1 * xsx]);
         } else {
             const int sy = min((int)floorf((float)oy * sh), ih - 1);
             const int sx = min((int)floorf((float)ox * sw), iw - 1);
@@ -72,10 +82,10 @@ __global__ __launch_bounds__(256) void resize_nhwc4_kernel(const float *__restri
                 const float *b0 = xb + (long long)y0 * xsy + 4 * cq, *b1 = xb + (long long)y1 * xsy + 4 * cq;
                 const float4 a = *(const float4 *)(b0 + x0 * xsx), b = *(const float4 *)(b0 + x1 * xsx);
                 const float4 cc = *(const float4 *)(b1 + x0 * xsx), d = *(const float4 *)(b1 + x1 * xsx);
-                v.x = ly0 * (lx0 * a.x + lx1 * b.x) + ly1 * (lx0 * cc.x + lx1 * d.x);
-                v.y = ly0 * (lx0 * a.y + lx1 * b.y) + ly1 * (lx0 * cc.y + lx1 * d.y);
-                v.z = ly0 * (lx0 * a.z + lx1 * b.z) + ly1 * (lx0 * cc.z + lx1 * d.z);
-                v.w = ly0 * (lx0 * a.w + lx1 * b.w) + ly1 * (lx0 * cc.w + lx1 * d.w);
+                v.x = bilin_sum(ly0, ly1, lx0, lx1, a.x, b.x, cc.x, d.x);
+                v.y = bilin_sum(ly0, ly1, lx0, lx1, a.y, b.y, cc.y, d.y);
+                v.z = bilin_sum(ly0, ly1, lx0, lx1, a.z, b.z, cc.z, d.z);
+                v.w = bilin_sum(ly0, ly1, lx0, lx1, a.w, b.w, cc.w, d.w);
             } else {
                 const int sx = min((int)floorf((float)ox * sw), iw - 1);
                 v = *(const float4 *)(xb + (long long)sy * xsy + sx * xsx + 4 * cq);
@@ -89,8 +99,8 @@ __global__ __launch_bounds__(256) void resize_nhwc4_kernel(const float *__restri
 // view: one thread = one channel quad of one source pixel -> the 2x2 output quad it centres.  The
 // 3x3 source neighbourhood (rows / columns clamped to the image) is loaded once, 9 float4 loads for
 // 4 outputs, and each output takes its 4 taps from those registers by the same index / weight rule
-// (bilin_index) and expression as resize_nhwc4_kernel, so the result is the generic kernel's bit for
-// bit.  (Loading each output's 4 taps separately, 16 loads with the centre pixel requested 4 times,
+// (bilin_index) and the same fma sequence (bilin_sum) as resize_nhwc4_kernel, so the result is the generic
+// kernel's bit for bit (tests/test_norm_direct_gpu.py asserts it).  (Loading each output's 4 taps separately, 16 loads with the centre pixel requested 4 times,
 // returned wrong data in the upper quarter-wave under two concurrently replayed graphs on MI355X:
 // tools/dbg_lanes4.py)
 __device__ __forceinline__ float4 sel3(int k, const float4 &a, const float4 &b, const float4 &c) {
@@ -135,10 +145,10 @@ __global__ __launch_bounds__(256) void up2_bilinear_nhwc4_kernel(const float *__
             auto lerp4 = [&](int y0, int y1, int x0, int x1, float ly0, float ly1, float lx0, float lx1) {
                 const float4 a = tap(y0, x0), b = tap(y0, x1), c = tap(y1, x0), d = tap(y1, x1);
                 float4 v;
-                v.x = ly0 * (lx0 * a.x + lx1 * b.x) + ly1 * (lx0 * c.x + lx1 * d.x);
-                v.y = ly0 * (lx0 * a.y + lx1 * b.y) + ly1 * (lx0 * c.y + lx1 * d.y);
-                v.z = ly0 * (lx0 * a.z + lx1 * b.z) + ly1 * (lx0 * c.z + lx1 * d.z);
-                v.w = ly0 * (lx0 * a.w + lx1 * b.w) + ly1 * (lx0 * c.w + lx1 * d.w);
+                v.x = bilin_sum(ly0, ly1, lx0, lx1, a.x, b.x, c.x, d.x);
+                v.y = bilin_sum(ly0, ly1, lx0, lx1, a.y, b.y, c.y, d.y);
+                v.z = bilin_sum(ly0, ly1, lx0, lx1, a.z, b.z, c.z, d.z);
+                v.w = bilin_sum(ly0, ly1, lx0, lx1, a.w, b.w, c.w, d.w);
                 return v;
             };
             *(float4 *)(y0r + (2 * ix) * ysx + 4 * cq) = lerp4(ya0, ya1, xa0, xa1, la0, la1, ma0, ma1);

@@ -501,15 +501,16 @@ __global__ __launch_bounds__(256) void in_apply_v(const float *__restrict__ x, i
         *(float4 *)(yb + (long long)p * ycs) = o;
         if (yp) {
             // reflect pad 1 (F.pad 'reflect'): pixel (r, q) lands at (r + 1, q + 1) and, on the second /
-            // second-to-last row or column, also on the mirrored border row / column
+            // second-to-last row or column, also on the mirrored border row / column.  The two tests are
+            // independent: in a 3-row plane row 1 is both, and mirrors onto row 0 and row h + 1.
             const int h = hw / w, r = p / w, q = p - r * w, W2 = w + 2;
-            const int rows[2] = {r + 1, r == 1 ? 0 : (r == h - 2 ? h + 1 : -1)};
-            const int cols[2] = {q + 1, q == 1 ? 0 : (q == w - 2 ? w + 1 : -1)};
+            const int rows[3] = {r + 1, r == 1 ? 0 : -1, r == h - 2 ? h + 1 : -1};
+            const int cols[3] = {q + 1, q == 1 ? 0 : -1, q == w - 2 ? w + 1 : -1};
             float *pb = yp + (long long)n * (h + 2) * W2 * ypcs + cc;
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 3; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
+                for (int j = 0; j < 3; ++j)
                     if (rows[i] >= 0 && cols[j] >= 0)
                         *(float4 *)(pb + ((long long)rows[i] * W2 + cols[j]) * ypcs) = o;
         }

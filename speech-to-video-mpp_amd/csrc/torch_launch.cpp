@@ -560,7 +560,8 @@ int64_t layernorm2d_(const Tensor &x, const Tensor &weight, const Tensor &bias, 
     const at::Device dev = x.device();
     const NV xv = nhwc(x, dev, "layernorm2d x"), yv = nhwc(y, dev, "layernorm2d y");
     const int f = pool ? 2 : 1;
-    TORCH_CHECK(yv.n == xv.n && yv.h * f == xv.h && yv.w * f == xv.w && yv.c == xv.c, "layernorm2d: y shape");
+    // pooled: F.avg_pool2d(.., 2) sizes, the last row / column of an odd image is dropped
+    TORCH_CHECK(yv.n == xv.n && yv.h == xv.h / f && yv.w == xv.w / f && yv.c == xv.c, "layernorm2d: y shape");
     const float *wp = vec(weight, dev, xv.c, "layernorm2d weight"), *bp = vec(bias, dev, xv.c, "layernorm2d bias");
     const float *rp = nullptr;
     int rcs = 0;

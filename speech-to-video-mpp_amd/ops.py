@@ -1023,6 +1023,8 @@ def conv_splits(ctx: Ctx, p) -> int:
 
 def layernorm2d(ctx: Ctx, x: NHWC, weight, bias, y: NHWC, *, act=ACT_LRELU, alpha=0.1, pool=False,
                 res: NHWC | None = None, eps=1e-5):
+    """LayerNorm over (H, W, C) + affine + act (+ 2x2 mean when ``pool``) (+ res).  Pooled, y and res are
+    [n, h // 2, w // 2, c]: the last row / column of an odd image is dropped, as F.avg_pool2d drops it."""
     rv = None if res is None else res.v
     _with_ws(ctx, lambda ws: S2V.layernorm2d_(x.v, weight, bias, eps, act, alpha, pool, rv, y.v, ws))
     return y
@@ -1031,7 +1033,8 @@ def layernorm2d(ctx: Ctx, x: NHWC, weight, bias, y: NHWC, *, act=ACT_LRELU, alph
 def instnorm(ctx: Ctx, x: NHWC, y: NHWC, gamma=None, beta=None, *, act=ACT_NONE, alpha=0.0,
              res: NHWC | None = None, eps=1e-5, pad_out: NHWC | None = None):
     """InstanceNorm2d (+ ADAIN: gamma / beta [N, C] row views) + act (+ res).  ``pad_out``
-    ([n, h+2, w+2, c] view) also receives F.pad(y, (1, 1, 1, 1), 'reflect')."""
+    ([n, h+2, w+2, c] view) also receives F.pad(y, (1, 1, 1, 1), 'reflect'): any h, w >= 2, on the
+    float4 path only (c % 4 == 0, 16-byte aligned views; anything else is refused)."""
     if pad_out is not None:
         assert (pad_out.n, pad_out.h, pad_out.w, pad_out.c) == (x.n, x.h + 2, x.w + 2, x.c)
     rv, pv = None if res is None else res.v, None if pad_out is None else pad_out.v
