@@ -917,6 +917,68 @@ int s2v_fan_crop(const unsigned char *frames, int n, int h, int w, const int *ta
 int s2v_fan_peaks(const float *hm, int n, int h, int w, int c, long long cs, float *preds, float *vals,
                   s2v_stream_t stream);
 
+/* ---- geometry between the preprocessing networks (S3FD -> FAN -> 3DMM regressor -> DNet) ---------- */
+
+/* get_preds_fromhm's preds_orig (utils.py:163-168): the heatmap points of s2v_fan_peaks in frame coordinates.
+ * preds: device fp32 [faces][k][2] (x, y), as s2v_fan_peaks writes them; mats: device fp32 [faces][6], rows 0
+ * and 1 of the face's INVERSE matrix, utils.transform's torch.inverse(t) (utils.py:77-85) as the host computes
+ * it for the crop table.  The matrix is data: torch.inverse's LU result is not what a closed form gives (its
+ * off-diagonal entries and m[2][2] - 1 are often not zero), so it is not re-derived here.  Per point and row
+ * (m0, m1, m2) of the matrix:
+ *   1. v = (m0 x + m1 y) + m2 in fp32, every product and sum rounded on its own (no FMA), in that order;
+ *   2. v is truncated toward zero (torch's .int());
+ *   3. the integer is stored as fp32: out [faces][k][2].
+ * This order equals torch.matmul(t, (x, y, 1)) on the host; an FMA chain from the constant term and an fp64
+ * accumulation both differ from it on points that land next to an integer.  Non-finite values and values
+ * outside int32 are outside the contract. */
+int s2v_fan_landmarks(const float *preds, const float *mats, int faces, int k, float *out, s2v_stream_t stream);
+/* facing.py:110-116 and align_img's parameters (util/preprocess.py:18-43 POS, :147-158 resize_n_crop_img,
+ * :173-179 extract_5p, :186-216) for n frames of w0 x h0 pixels, with the fit validation of
+ * inference._usable_landmarks.  lms: device fp32 [n][68][2], (x, y) image coordinates (y down).  A frame whose
+ * 136 values all equal -1 is a frame without landmarks; the reference tests np.mean(lm) == -1, which differs
+ * only on landmarks whose mean is -1 by accident.  pinv: HOST fp64 [4][5], np.linalg.pinv([lm3D | 1]): POS's
+ * 10 x 8 system is two copies of that 5 x 4 one, one per axis.  Per frame with landmarks:
+ *   1. y' = float32(h0 - 1) - y in fp32 (facing.py:115);
+ *   2. extract_5p in fp32: points 31, (37, 40), (43, 46), 49, 55 (1-based), a two-point mean
+ *      float32(float32(a + b) / 2), then the order [1, 2, 0, 3, 4];
+ *   3. from here in fp64, unfused: kx = pinv p5[:, 0], ky = pinv p5[:, 1] (sums in index order), t = (kx[3],
+ *      ky[3]), s = rescale_factor / ((|kx[0:3]| + |ky[0:3]|) / 2), w = int(w0 s), h = int(h0 s),
+ *      left = int((w / 2 - target_size / 2) + (t0 - w0 / 2) s), up = int((h / 2 - target_size / 2) +
+ *      (h0 / 2 - t1) s); every int() truncates toward zero.
+ * A fit is rejected when w <= 0 or h <= 0, when w0 / w or h0 / h exceeds 11.5 (s2v_pil_resize_crop's tap
+ * limit, face3d.MAX_DOWNSCALE), or when one of the four values before truncation is not finite or reaches 2^31
+ * in magnitude.  A frame without landmarks and a frame with a rejected fit take the fit of the no-landmark
+ * points (lm3D[:, :2] + 1) / 2 * (w0, h0) of facing.py:112-113 instead.  That fit is the same for every such
+ * frame and is NOT made here: default_box (HOST int32 [4] = (w, h, left, up)) and default_trans (HOST fp32 [5])
+ * are align_img's own result for those points, computed once per frame size on the host.  The points are an
+ * affine image of lm3D itself, so their fit is exact: w / 2 - target_size / 2 + 0 s is an integer or a half, and
+ * the rounding error of t (1e-13) alone decides which way int() goes.  Two float64 routes do not agree on that
+ * (pinv and lstsq give left, up = -10, -9 and -9, -10 for a 1400 x 1400 frame), so the host's result is data.
+ * params: device int32 [n][4] = (w, h, left, up), the block s2v_pil_resize_crop reads; trans: device fp32 [n][5]
+ * = (w0, h0, s, t0, t1), rounded from fp64 once (semantic's trans_params, facing.py:125-129); status: device
+ * int32 [n]: 0 fitted from the landmarks, 1 no landmarks, 2 the landmarks' fit was rejected.  On landmarks the
+ * pseudo-inverse route and POS's lstsq agree to about 1e-12 relative: the same boxes wherever no value before
+ * truncation lies that close to an integer, and trans within one fp32 ulp. */
+int s2v_face3d_align(const float *lms, int n, int w0, int h0, const int *default_box, const float *default_trans,
+                     const double *pinv, double target_size, double rescale_factor, int *params, float *trans,
+                     int *status, s2v_stream_t stream);
+/* The DNet coefficient windows of facing.py:176-187 (inference_utils.py:73-99) for frames [start, stop) of a
+ * clip: semantic device fp32 [n_frames][262] -> out device fp32 [stop - start][73][26].  Window idx holds the 26
+ * frames idx - 13 .. idx + 12, each clamped to [0, n_frames - 1], as columns; its 73 rows are semantic's columns
+ * 80:144 (expression), 224:227 (angles), 254:257 (translation) and 259:262 (crop).  Row 70 (column 259) is
+ * multiplied by the ratio in fp32 unless the ratio is exactly 0 (the reference's `if crop_norm_ratio:`; a NaN
+ * ratio multiplies); with expression (device fp32 [64]; NULL: none) rows 0..63 hold expression[row] in every
+ * column.
+ * The ratio needs no floating-point reduction.  find_crop_norm_ratio takes the argmin over the clip's frames
+ * of 0.3 mean|exp - exp_src| + 0.7 mean|angle - angle_src|, a sum of non-negative terms.  It is exactly 0 for
+ * the source frame against itself, so the minimum is 0, and argmin returns the first frame where it is 0.  The
+ * sum is 0 for a frame only if each of its 67 values compares equal to the source's (-0 equals +0).  So the
+ * index is the first frame j whose columns 80:144 and 224:227 compare equal to the source's, and the ratio is
+ * float32(src[259] / semantic[j][259]).  The source is frame idx, or frame 0 with one_shot.  Rows holding NaN,
+ * and differences so small that their mean underflows to 0, are outside the contract. */
+int s2v_dnet_windows(const float *semantic, int n_frames, int start, int stop, const float *expression,
+                     int one_shot, float *out, s2v_stream_t stream);
+
 /* ---- GANimation upper-face editing (third_part/ganimation_replicate; inference.py:269-288) ---- */
 
 /* The SplitGenerator input (model_utils.py:474-478) of n uint8 HWC originals [h][w][3] (element (b, y, x, ch)

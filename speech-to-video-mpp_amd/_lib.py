@@ -173,6 +173,10 @@ _SIGS = {
                                _vp, _vp, _vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp]),
     "s2v_fan_crop": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp]),
     "s2v_fan_peaks": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _vp, _vp, _vp]),
+    "s2v_fan_landmarks": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
+    "s2v_face3d_align": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp,
+                                  _vp, _vp, _vp]),
+    "s2v_dnet_windows": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp]),
     "s2v_warp_affine": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _c_int, _vp, _vp, _c_int, _c_int,
                                  _c_ll, _c_ll, _vp]),
     "s2v_face_paste": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp] + [_c_int] * 6 + [_vp]),

@@ -16,6 +16,12 @@ fixed-point arithmetic, bit-exact) straight into the NHWC input of the ResNet-50
 are an input of the extractor, as the reference's own cache file ``*_landmarks.txt`` is;
 KeypointExtractor (extract_kp_videos.py:15-57) produces them with face_detection.FaceAlignment's FAN
 network.
+
+Opt-in (geometry_mode, inference's --geometry device): the fits run on the device too.  align_device
+(s2v_face3d_align) makes them for a whole clip from landmarks in device memory, POS as the pseudo-inverse of
+[lm3D | 1] in float64, with the validation of inference._usable_landmarks; Face3DExtractor.semantic_device
+chains it with the resize-crop and the network without a copy, and KeypointExtractor.extract_keypoint_device
+leaves the landmarks on the device.
 """
 from __future__ import annotations
 
@@ -32,6 +38,24 @@ TARGET = 224
 RESCALE = 102.0
 PIL_BILINEAR, PIL_BICUBIC = 2, 3
 MAX_DOWNSCALE = 11.5        # s2v_pil_resize_crop: at most 48 taps per output coordinate
+
+
+GEOMETRY_ENV = "S2V_GEOMETRY"
+GEOMETRY_MODES = ("host", "device")
+ALIGN_FITTED, ALIGN_NO_LANDMARKS, ALIGN_REJECTED = range(3)      # s2v_face3d_align's status
+
+
+def geometry_mode(name="host") -> str:
+    """The ``geometry=`` argument of inference.run: where the arithmetic between the preprocessing networks runs
+    (the landmarks' map back to the frame, align_img's parameters and their validation, the DNet coefficient
+    windows): "host" (the default) or "device"; None reads S2V_GEOMETRY (unset or empty: "host").  Anything
+    else raises ValueError."""
+    source = "geometry="
+    if name is None:
+        name, source = os.environ.get(GEOMETRY_ENV) or "host", GEOMETRY_ENV + "="
+    if name not in GEOMETRY_MODES:
+        raise ValueError(f"{source}{name!r}: {GEOMETRY_ENV} / geometry= takes one of {', '.join(GEOMETRY_MODES)}")
+    return name
 
 
 def load_lm3d(bfm_folder):
@@ -139,6 +163,49 @@ def resize_crop_params(ctx, frames: torch.Tensor, params: torch.Tensor, out: NHW
                                       out.h, out.w, out.cs, ctx.stream), "s2v_pil_resize_crop")
 
 
+def default_fit(lm3d_std, W, H, target_size=float(TARGET), rescale_factor=RESCALE):
+    """align_img's parameters of a frame without landmarks (facing.py:112-113: the points (lm3d + 1) / 2 * (W,
+    H)), as coeffs computes them for every such frame -> ((w, h, left, up), trans float32 [5]).  Raises ValueError
+    when s2v_pil_resize_crop cannot take the box, as box_params does."""
+    lm3d_std = np.asarray(lm3d_std)
+    lm = frame_landmarks(np.full((68, 2), -1.0, np.float32), W, H, lm3d_std)
+    t, box, _ = align_params(W, H, lm, lm3d_std, target_size, rescale_factor)
+    _check_scale(W, H, box[0], box[1])
+    return box, np.array([float(v) for v in t], dtype=np.float32)
+
+
+def pos_pinv(lm3D) -> np.ndarray:
+    """np.linalg.pinv([lm3D | 1]) as float64 [4, 5]: POS's 10 x 8 least-squares system is this 5 x 4 one twice,
+    once per image axis, so k[0:4] = pinv @ x and k[4:8] = pinv @ y."""
+    lm3D = np.asarray(lm3D, np.float64)
+    return np.ascontiguousarray(np.linalg.pinv(np.concatenate([lm3D, np.ones((lm3D.shape[0], 1))], 1)))
+
+
+def align_device(ctx, lms: torch.Tensor, W, H, lm3D, target_size=float(TARGET), rescale_factor=RESCALE, pinv=None,
+                 default=None):
+    """s2v_face3d_align: frame_landmarks + align_params + inference._usable_landmarks for every frame in one
+    launch.  ``lms``: device float32 [n, 68, 2] (all -1: no landmarks) -> (params int32 [n, 4] = (w, h, left,
+    up) for resize_crop_params, trans float32 [n, 5], status int32 [n]: ALIGN_*) on the device.  ``pinv`` /
+    ``default``: pos_pinv(lm3D) and default_fit(lm3D, W, H, ...) when the caller keeps them.  The no-landmark
+    fit is the host's, made once: frames without landmarks or with a rejected fit get exactly the host route's
+    box.  No copy, no synchronisation."""
+    n = lms.shape[0]
+    if not (lms.is_cuda and lms.dtype == torch.float32 and lms.is_contiguous() and tuple(lms.shape[1:]) == (68, 2)):
+        raise ops._lib.S2VError("align_device: lms must be a contiguous float32 [n, 68, 2] HIP tensor")
+    params = torch.empty((n, 4), dtype=torch.int32, device=lms.device)
+    trans = torch.empty((n, 5), dtype=torch.float32, device=lms.device)
+    status = torch.empty((n,), dtype=torch.int32, device=lms.device)
+    if n == 0:
+        return params, trans, status
+    box, dtrans = default_fit(lm3D, W, H, target_size, rescale_factor) if default is None else default
+    box, dtrans = np.asarray(box, np.int32).reshape(4), np.ascontiguousarray(dtrans, np.float32).reshape(5)
+    pinv = pos_pinv(lm3D) if pinv is None else np.ascontiguousarray(pinv, np.float64)
+    check(ctx.lib.s2v_face3d_align(lms.data_ptr(), n, int(W), int(H), box.ctypes.data, dtrans.ctypes.data,
+                                   pinv.ctypes.data, float(target_size), float(rescale_factor), params.data_ptr(),
+                                   trans.data_ptr(), status.data_ptr(), ctx.stream), "s2v_face3d_align")
+    return params, trans, status
+
+
 def align_img(img, lm, lm3D, mask=None, target_size=float(TARGET), rescale_factor=RESCALE):
     """preprocess.py:186-216 on the device: img uint8 HWC RGB tensor -> (trans_params, im_new fp32
     [224, 224, 3] = np.array(img_new) / 255. as facing.py:120 uses it, lm_new, None)."""
@@ -204,6 +271,36 @@ class KeypointExtractor:
             np.savetxt(os.path.splitext(name)[0] + '.txt', keypoints.reshape(-1))
         return keypoints
 
+    def extract_keypoint_device(self, images) -> torch.Tensor:
+        """extract_keypoint for a list of frames (or one [N,H,W,3] array / device tensor) with the points left
+        on the device: float32 [N, 68, 2], by the same rules (the first face of a frame; a frame without a
+        face takes the previous frame's points, all -1 when there are none yet; ``misses`` counts them).  Needs
+        a detector whose get_landmarks_from_batch takes on_device=True.  Which frames have a face is known on
+        the host from the detector's boxes, so the rules are one index_select over the faces' points."""
+        first, rows, faces, dev = [], [], 0, None
+        for s in range(0, len(images), self.batch):
+            chunk = images[s: s + self.batch]
+            if not isinstance(chunk, torch.Tensor):
+                chunk = (torch.stack(list(chunk)) if isinstance(chunk[0], torch.Tensor)
+                         else np.stack([np.asarray(im) for im in chunk]))
+            pts, index = self.detector.get_landmarks_from_batch(chunk, on_device=True)
+            dev = pts.device
+            rows.append(pts)
+            for i in range(len(chunk)):
+                first.append(faces + index.index(i) if i in index else -1)
+            faces += len(index)
+        if dev is None:
+            raise ValueError("extract_keypoint_device: no frames")
+        take, last = [], faces                            # row ``faces`` is the all -1 frame
+        for f in first:
+            if f < 0:
+                self.misses += 1
+            else:
+                last = f
+            take.append(last)
+        table = torch.cat(rows + [torch.full((1, 68, 2), -1.0, device=dev)])
+        return table.index_select(0, torch.tensor(take, dtype=torch.long).to(dev))
+
 
 class Face3DExtractor:
     """facing.py:100-130 face_3dmm_extraction (+ :136-165 hack_3dmm_expression's image branch) on a
@@ -216,6 +313,7 @@ class Face3DExtractor:
         self.device = torch.device(device)
         self.batch = batch
         self.ctx = ops.Ctx(self.device)
+        self._pinv, self._default = None, {}            # semantic_device: pos_pinv(lm3d), default_fit per frame size
 
     def coeffs(self, frames: torch.Tensor, lms) -> tuple[np.ndarray, np.ndarray]:
         """frames uint8 [N, H, W, 3] RGB on the device, lms [N, 68, 2] (x, y image coordinates, or
@@ -237,6 +335,33 @@ class Face3DExtractor:
             out[s:e] = self.net.forward_nhwc(xv)
         torch.cuda.current_stream(self.device).synchronize()
         return out.cpu().numpy(), np.stack(trans)
+
+    def semantic_device(self, frames: torch.Tensor, lms_dev: torch.Tensor):
+        """face_3dmm_extraction with the front end on the device: frames uint8 [N, H, W, 3] RGB and ``lms_dev``
+        float32 [N, 68, 2] (all -1: no landmarks), both on the device -> (semantic [N, 262] float32, status [N]
+        int32: ALIGN_*), both on the device.  One s2v_face3d_align launch for the clip, then coeffs' batches:
+        resize_crop_params and the ResNet-50 forward.  A fit that inference._usable_landmarks rejects takes the
+        no-landmark fit (status ALIGN_REJECTED); that fit is the host's (default_fit, once per frame size).  No
+        host copy and no synchronisation here."""
+        N, H, W, _ = frames.shape
+        if lms_dev.shape[0] != N:
+            raise ValueError(f"semantic_device: {N} frames, {lms_dev.shape[0]} landmark sets")
+        frames = frames.contiguous()
+        if (W, H) not in self._default:
+            self._default[(W, H)] = default_fit(self.lm3d, W, H)
+        if self._pinv is None:
+            self._pinv = pos_pinv(self.lm3d)
+        params, trans, status = align_device(self.ctx, lms_dev.contiguous(), W, H, self.lm3d, pinv=self._pinv,
+                                             default=self._default[(W, H)])
+        out = torch.empty((N, 262), dtype=torch.float32, device=self.device)
+        out[:, 257:] = trans
+        x4 = NHWC.empty(min(self.batch, N), TARGET, TARGET, 4, self.device)
+        for s in range(0, N, self.batch):
+            e = min(N, s + self.batch)
+            xv = x4 if e - s == x4.n else NHWC(x4.t[: e - s])
+            resize_crop_params(self.ctx, frames[s:e], params[s:e], xv)
+            out[s:e, :257] = self.net.forward_nhwc(xv)
+        return out, status
 
     def face_3dmm_extraction(self, frames: torch.Tensor, lms) -> np.ndarray:
         """-> semantic_npy [N, 262] float32: [id, exp, tex, angle, gamma, trans, trans_params]

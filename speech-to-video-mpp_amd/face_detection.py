@@ -24,7 +24,9 @@ third_part/face3d/extract_kp_videos.py:15-57 calls) run on the device as well: u
 face of a batch in one launch (s2v_fan_crop), the FAN network (models.FAN) and get_preds_fromhm's argmax
 and quarter-pixel step (s2v_fan_peaks); one device -> host copy per batch brings the 68 heatmap points per
 face, and their map back to frame coordinates (utils.transform's float32 matrix and .int()) stays on the
-host, as the reference computes it.
+host, as the reference computes it.  With get_landmarks_from_batch(on_device=True) (opt-in) that map runs on
+the device too (s2v_fan_landmarks over the host's inverse matrices, uploaded with the crop table) and the
+points stay there.
 
 Per-image equivalence with the reference's batched post-processing.  batch_detect (detect.py:77-92)
 collects the UNION over the batch of the positions whose score passes 0.05 in any image, once per
@@ -198,6 +200,7 @@ class SFDDetector:
 
 # ----------------------------------------------------------------------------- FAN landmarks
 FAN_RESOLUTION = 256.0                  # utils.crop's default resolution: the network input side
+HEATMAP_SIZE = 64                       # the heatmaps' side at that input (s2v_fan_peaks takes no other)
 # The glue between the detector and the network, get_landmarks_from_image, lives in the face-alignment
 # 1.3.5 package, which is not part of the reference tree.  It adds two facts that stay parity-unpinned
 # (no reference code or fixture pins them); everything else here restates reference code:
@@ -274,6 +277,12 @@ def preds_to_image(preds, center, scale, hm_size=64) -> torch.Tensor:
     return out
 
 
+def back_map_matrix(center, scale, hm_size=64) -> np.ndarray:
+    """Rows 0 and 1 of preds_to_image's matrix, transform_matrix(center, scale, hm_size, True), as float32 [6]:
+    s2v_fan_landmarks takes the host's torch.inverse result as data."""
+    return transform_matrix(center, scale, hm_size, True)[:2].reshape(6).numpy().copy()
+
+
 class FaceAlignment:
     """api.py:46-79, plus the landmark half of face_alignment.FaceAlignment (get_landmarks_from_image /
     get_landmarks_from_batch) over the FAN network.  ``detector``: an SFDDetector; without it one is built
@@ -310,11 +319,13 @@ class FaceAlignment:
         self.fan_passes += 1
         return self.face_alignment_net.heatmaps(x4)[0][HEATMAP_STACK]
 
-    def crops(self, frames: torch.Tensor, table: np.ndarray) -> NHWC:
-        """s2v_fan_crop: the 256x256 network inputs [faces, 256, 256, 4] of the table's faces."""
+    def crops(self, frames: torch.Tensor, table: np.ndarray, dev_table: torch.Tensor | None = None) -> NHWC:
+        """s2v_fan_crop: the 256x256 network inputs [faces, 256, 256, 4] of the table's faces.  ``dev_table``:
+        the table in device memory already (face_tables), else it is uploaded here."""
         n, H, W, _ = frames.shape
         host = np.ascontiguousarray(table, np.int32)
-        dev_table = torch.from_numpy(host).to(frames.device)
+        if dev_table is None:
+            dev_table = torch.from_numpy(host).to(frames.device)
         size = int(FAN_RESOLUTION)
         x4 = NHWC.empty(len(host), size, size, 4, frames.device)
         ctx = post._ctx(frames.device)
@@ -322,24 +333,55 @@ class FaceAlignment:
                                    ctx.stream), "s2v_fan_crop")
         return x4
 
-    def peaks(self, hm: NHWC):
+    def peaks(self, hm: NHWC, on_device=False, k=None):
         """s2v_fan_peaks on heatmaps [faces, 64, 64, cs] -> (preds [faces, 68, 2], peak values [faces, 68])
-        float32 host tensors: one device -> host copy."""
-        from .models.fan_arch import NUM_LANDMARKS as K
+        float32 host tensors: one device -> host copy.  ``on_device``: the two stay on the device (views of one
+        buffer) and nothing is copied.  ``k``: the number of leading channels that are landmarks (default 68)."""
+        from .models.fan_arch import NUM_LANDMARKS
+        K = NUM_LANDMARKS if k is None else int(k)
         buf = torch.empty((hm.n, K * 3), device=hm.t.device)
         ctx = post._ctx(hm.t.device)
         check(ctx.lib.s2v_fan_peaks(hm.ptr, hm.n, hm.h, hm.w, K, hm.cs, buf.data_ptr(), buf.data_ptr() + 4 * hm.n * K * 2,
                                     ctx.stream), "s2v_fan_peaks")
-        host = buf.cpu().reshape(-1)
-        return host[: hm.n * K * 2].reshape(hm.n, K, 2), host[hm.n * K * 2:].reshape(hm.n, K)
+        flat = buf.reshape(-1) if on_device else buf.cpu().reshape(-1)
+        return flat[: hm.n * K * 2].reshape(hm.n, K, 2), flat[hm.n * K * 2:].reshape(hm.n, K)
+
+    def face_tables(self, table: np.ndarray, mats: np.ndarray, device):
+        """The crop table int32 [faces, 5] and the back-map matrices float32 [faces, 6] in one upload -> their
+        two device views."""
+        f = len(table)
+        host = np.empty(f * 11, np.int32)
+        host[: f * 5] = np.ascontiguousarray(table, np.int32).reshape(-1)
+        host[f * 5:] = np.ascontiguousarray(mats, np.float32).reshape(-1).view(np.int32)
+        dev = torch.from_numpy(host).to(device)
+        return dev[: f * 5].view(f, 5), dev[f * 5:].view(torch.float32).view(f, 6)
+
+    def landmarks_device(self, preds: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
+        """s2v_fan_landmarks: device heatmap points [faces, k, 2] through the device matrices [faces, 6]
+        (back_map_matrix) -> device float32 [faces, k, 2] of integer-valued frame coordinates: preds_to_image
+        for every face in one launch."""
+        f, k, _ = preds.shape
+        if not (preds.is_cuda and preds.dtype == torch.float32 and preds.is_contiguous() and mats.is_cuda and
+                mats.dtype == torch.float32 and mats.is_contiguous() and tuple(mats.shape) == (f, 6)):
+            raise TypeError("landmarks_device: contiguous float32 device preds [faces, k, 2] and mats [faces, 6]")
+        out = torch.empty_like(preds)
+        if f == 0:
+            return out
+        ctx = post._ctx(preds.device)
+        check(ctx.lib.s2v_fan_landmarks(preds.data_ptr(), mats.data_ptr(), f, k, out.data_ptr(), ctx.stream),
+              "s2v_fan_landmarks")
+        return out
 
     @torch.no_grad()
-    def get_landmarks_from_batch(self, images, detected_faces=None):
+    def get_landmarks_from_batch(self, images, detected_faces=None, on_device=False):
         """images uint8 [B,H,W,3] RGB (host or device) -> per image None, or a list with one float32
         [68, 2] array of (x, y) frame coordinates per face, in the detector's order.  ``detected_faces``:
         per image a list of [x1, y1, x2, y2, ...] rows (else S3FD on the channel-flipped frames, as
         get_detections_for_batch).  Per face: centre / scale (box_center_scale), utils.crop, FAN,
-        get_preds_fromhm on the last stack (flip_input: plus the flipped pass, utils.flip), preds_orig."""
+        get_preds_fromhm on the last stack (flip_input: plus the flipped pass, utils.flip), preds_orig.
+        ``on_device``: -> (device float32 [faces, 68, 2], the image index of every face as a host list), the
+        same points with preds_orig on the device (s2v_fan_landmarks): the per-face inverse matrices go up
+        with the crop table, nothing comes back and no per-point host work is done."""
         if self.face_alignment_net is None:
             raise RuntimeError("FaceAlignment: no FAN network (pass fan= or path_to_fan=)")
         t = _batch(images, self.device)
@@ -350,11 +392,18 @@ class FaceAlignment:
         index = [i for i, dets in enumerate(detected_faces) for _ in dets]
         results = [None] * t.shape[0]
         if not index:
+            if on_device:
+                from .models.fan_arch import NUM_LANDMARKS
+                return torch.empty((0, NUM_LANDMARKS, 2), device=t.device), index
             return results
         ref = self.face_detector.reference_scale
         cs = [box_center_scale(d, ref) for dets in detected_faces for d in dets]
         table = crop_table(index, [c for c, _ in cs], [s for _, s in cs], t.shape[1:3])
-        x4 = self.crops(t, table)
+        dev_table = mats = None
+        if on_device:
+            dev_table, mats = self.face_tables(table, np.stack([back_map_matrix(c, s, HEATMAP_SIZE) for c, s in cs]),
+                                               t.device)
+        x4 = self.crops(t, table, dev_table)
         hm = self._fan(x4)
         if self.flip_input:
             # out += flip(net(flip(inp))[-1], is_label=True): columns reversed, landmark channels paired
@@ -365,6 +414,10 @@ class FaceAlignment:
             back = hf.t[..., :k].index_select(2, self._flip_index(hf.w, dev))
             back = back.index_select(3, torch.tensor(list(self.flip_pairs), dtype=torch.long, device=dev))
             hm = NHWC((hm.t[..., :k] + back).contiguous())
+        if on_device:
+            if hm.h != HEATMAP_SIZE:
+                raise ValueError(f"get_landmarks_from_batch: {hm.h}x{hm.w} heatmaps, the matrices are for {HEATMAP_SIZE}")
+            return self.landmarks_device(self.peaks(hm, on_device=True)[0], mats), index
         preds, _ = self.peaks(hm)
         for f, (i, (c, s)) in enumerate(zip(index, cs)):
             pts = preds_to_image(preds[f], c, s, hm.h).numpy()

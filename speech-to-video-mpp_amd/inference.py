@@ -25,7 +25,9 @@ Steps (reference file:line in brackets):
     regresses them from the frames with the box-derived 5 landmarks; otherwise they are synthetic;
     with --landmarks the 68 FAN landmarks of every frame (facing.py:89-97: KeypointExtractor over S3FD +
     FAN, weights from <checkpoints>/s3fd.pth and 2DFAN4.pth or the synthetic presets) drive align_img
-    instead of the no-landmark path;
+    instead of the no-landmark path; with --geometry device the arithmetic between these networks (the landmarks'
+    map back to the frame, align_img's parameters and their validation, the DNet coefficient windows) runs on
+    the device as well, with the host routes' results;
   * DNet stabilisation of the box crop (trans_image: 256x256, [-1, 1], facing.py:177-191) with the
     coefficient windows, then ENet(LNet) on [masked crop, reference] batches of LNet_batch_size,
     clamp(0, 1) * 255 [inference.py:259-267, :393-399] (s2v_amd.pipeline.LipSyncPipeline);
@@ -262,11 +264,12 @@ def _usable_landmarks(lms, H, W, lm3d):
     return lms, rejects
 
 
-def _semantic(frames_bgr: torch.Tensor, ckpt_dir, dev, lms=None):
+def _semantic(frames_bgr: torch.Tensor, ckpt_dir, dev, lms=None, geometry="host"):
     """facing.py:100-130 face_3dmm_extraction on the frames: ReconNetWrapper('resnet50') from
     face3d_pretrain_epoch_20.pth (synthetic weights without it) -> [n, 262].  ``lms``: the frames' 68
     landmarks [n, 68, 2] (_landmarks); without them the reference's no-landmark path (all -1 landmarks ->
-    lm3d positions, facing.py:110-116)."""
+    lm3d positions, facing.py:110-116).  ``geometry`` "device": ``lms`` is a device tensor (_landmarks with
+    on_device) and Face3DExtractor.semantic_device runs -> ((semantic [n, 262], status [n]) on the device, kind)."""
     from . import face3d, models, synth
     from .models.face3d_arch import ReconNetWrapperParams
     path = os.path.join(ckpt_dir or "", "face3d_pretrain_epoch_20.pth")
@@ -282,21 +285,28 @@ def _semantic(frames_bgr: torch.Tensor, ckpt_dir, dev, lms=None):
     n = frames_bgr.shape[0]
     rgb = frames_bgr[..., [2, 1, 0]].contiguous()                               # facing.py reads RGB PIL frames
     ext = face3d.Face3DExtractor(net, lm3d, dev)
+    if geometry == "device":
+        if lms is None:
+            lms = torch.full((n, 68, 2), -1.0, device=dev)
+        return ext.semantic_device(rgb, lms), kind
     if lms is None:
         lms = np.full((n, 68, 2), -1.0, np.float32)
     return ext.face_3dmm_extraction(rgb, lms), kind
 
 
-def _landmarks(frames_bgr: torch.Tensor, ckpt_dir, dev, detector=None, nms="host"):
+def _landmarks(frames_bgr: torch.Tensor, ckpt_dir, dev, detector=None, nms="host", on_device=False):
     """facing.py:89-97: KeypointExtractor().extract_keypoint on the RGB frames -> (landmarks [n, 68, 2],
     FAN weight kind, frames without a face).  FAN weights from <checkpoints>/2DFAN4.pth, or the synthetic
-    FAN_SYNTH preset without it; the boxes come from the S3FD detector of _face_detector."""
+    FAN_SYNTH preset without it; the boxes come from the S3FD detector of _face_detector.  ``on_device``: the
+    landmarks stay on the device (extract_keypoint_device), float32 [n, 68, 2]."""
     from . import face3d
     if detector is None:
         detector, kind = _landmark_detector(ckpt_dir, dev, nms)
     else:
         kind = "given detector"
     kp = face3d.KeypointExtractor(detector)
+    if on_device:
+        return kp.extract_keypoint_device(frames_bgr[..., [2, 1, 0]].contiguous()), kind, kp.misses
     lms = kp.extract_keypoint(frames_bgr[..., [2, 1, 0]].contiguous(), info=False)
     return lms.astype(np.float32), kind, kp.misses
 
@@ -407,7 +417,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         landmarks: bool = False, landmark_detector=None, stitch: bool = False, stitch_detector=None,
         up_face: str = "original", without_rl1: bool = False, up_face_model=None, precision: str | None = None,
         nms: str | None = "host", fps: float = 25.0, jpeg_decode: str | None = "wave",
-        audio_load: str | None = "host"):
+        audio_load: str | None = "host", geometry: str | None = "host"):
     """-> dict(frames uint8 [n,H,W,3] device, preds uint8 [n,3,384,384], meta).  ``ref_enhance``:
     Step 5 with FaceEnhancement-512 (``ref_hook``: any callable on uint8 [b,3,h,w] references).
     ``enhance``: the per-frame tail of inference.py:296-330 on the pasted frames -> ``enhanced``
@@ -445,13 +455,20 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     S2V_JPEG_DECODE; ``meta["jpeg_decode"]`` records it.  ``audio_load``: where ``audio_path`` becomes float32 mono
     at 16 kHz: "host" (the default: load_wav, stdlib ``wave`` + NumPy), "device" (audio.load_audio: the file's sample
     bytes are decoded, downmixed and resampled in one launch; it also reads IEEE-float and EXTENSIBLE files, which
-    ``wave`` refuses) or None for S2V_AUDIO_LOAD; ``meta["audio_load"]`` records it."""
+    ``wave`` refuses) or None for S2V_AUDIO_LOAD; ``meta["audio_load"]`` records it.  ``geometry``: where the
+    arithmetic between the preprocessing networks runs: "host" (the default), "device" or None for S2V_GEOMETRY.
+    With "device" the landmarks' map back to the frame (s2v_fan_landmarks), align_img's parameters with the
+    validation of _usable_landmarks (s2v_face3d_align; ``landmark_rejects`` counts its status 2) and the DNet
+    coefficient windows (s2v_dnet_windows) run there, and ``semantic`` comes to the host once, at the end;
+    ``stitch`` keeps reading its own landmarks through the host.  ``meta["geometry"]`` records it."""
     kw = dict(locals())                                     # the arguments (nothing else is bound yet)
     from . import audio, mjpeg, ops, pipeline, post, synth
     from . import face as faces
     nms = kw["nms"] = faces.nms_mode(nms)                   # ValueError on a bad name before anything runs
     jpeg_decode = kw["jpeg_decode"] = mjpeg.jpeg_decode_mode(jpeg_decode)           # likewise
     audio_load = kw["audio_load"] = audio.audio_load_mode(audio_load)               # likewise
+    from . import face3d
+    geometry = kw["geometry"] = face3d.geometry_mode(geometry)                      # likewise
     if precision is not None:
         kw["precision"] = None
         with ops.precision(precision):                      # ValueError on a bad name before anything runs
@@ -517,12 +534,18 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
     from ._lib import check
     check(ctx.lib.s2v_u8_to_gan(crops.data_ptr(), n, 256, 256, src.data_ptr(), ctx.stream), "s2v_u8_to_gan")
     lms = None
-    if landmarks:
-        lms, lkind, lmiss = _landmarks(frames, ckpt_dir, dev, landmark_detector, nms)   # facing.py:89-97
-        lms, lrej = _usable_landmarks(lms, H, W, _lm3d(ckpt_dir))
-    semantic, skind = _semantic(frames, ckpt_dir, dev, lms)                        # facing.py:100-130
     expression = synth.hash_array("inference.expression", (64,), -1.0, 1.0)        # expression.mat is absent
-    coeffs = torch.from_numpy(pipeline.dnet_coefficients(semantic, expression, False, 0, n)).to(dev)
+    if geometry == "device":
+        if landmarks:
+            lms, lkind, lmiss = _landmarks(frames, ckpt_dir, dev, landmark_detector, nms, on_device=True)
+        (semantic_dev, fit_status), skind = _semantic(frames, ckpt_dir, dev, lms, geometry)
+        coeffs = pipeline.dnet_coefficients_device(semantic_dev, expression, False, 0, n)
+    else:
+        if landmarks:
+            lms, lkind, lmiss = _landmarks(frames, ckpt_dir, dev, landmark_detector, nms)   # facing.py:89-97
+            lms, lrej = _usable_landmarks(lms, H, W, _lm3d(ckpt_dir))
+        semantic, skind = _semantic(frames, ckpt_dir, dev, lms)                    # facing.py:100-130
+        coeffs = torch.from_numpy(pipeline.dnet_coefficients(semantic, expression, False, 0, n)).to(dev)
     if ref_enhance and ref_hook is None:
         ref_hook = _ref_enhancer(ckpt_dir, dev, nms)
     stitcher = None
@@ -584,7 +607,7 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
             "box": [y1, y2, x1, x2], "semantic": skind, "ref_enhance": ref_hook is not None,
             "restore": bool(enhance and restore), "up_face": up_face, "without_rl1": bool(without_rl1),
             "up_face_weights": ukind, "conv_arith": ops.PRECISION, "nms": nms, "jpeg_decode": jpeg_decode,
-            "audio_load": audio_load,
+            "audio_load": audio_load, "geometry": geometry,
             "seconds": round(time.time() - t0, 3)}
     if face_det:
         meta["boxes"] = [list(b) for b in boxes]
@@ -594,6 +617,9 @@ def run(face: str, audio_path: str, max_frames: int = 8, batch: int = 16, box_fr
         meta["stitch_misses"] = int(stitcher.misses)
         meta["stitch_landmarks"] = stkind
     res = {"frames": out, "preds": preds, "enhanced": enhanced, "meta": meta}
+    if landmarks and geometry == "device":                 # the one copy of the device route's results
+        semantic = semantic_dev.cpu().numpy()
+        lrej = int((fit_status == face3d.ALIGN_REJECTED).sum().item())
     if landmarks:
         meta["landmarks"] = lkind
         meta["landmark_misses"] = int(lmiss)
@@ -653,6 +679,11 @@ def build_parser():
     ap.add_argument("--audio_load", default=None, choices=["host", "device"],
                     help="where --audio is decoded, downmixed and resampled to 16 kHz (default: S2V_AUDIO_LOAD, else "
                          "host); device: one kernel launch on the file's sample bytes")
+    ap.add_argument("--geometry", default=None, choices=["host", "device"],
+                    help="where the arithmetic between the preprocessing networks runs: the landmarks' map back to "
+                         "the frame, align_img's parameters and their validation, the DNet coefficient windows "
+                         "(default: S2V_GEOMETRY, else host); device: three small kernels, no per-point or per-frame "
+                         "host work")
     ap.add_argument("--jpeg_quality", type=int, default=95,
                     help="with --outfile NAME.avi: JPEG quality 1..100 (the reference asks ffmpeg for its best, -q:v 1)")
     return ap
@@ -686,7 +717,8 @@ def main(argv=None):
             ref_enhance=a.ref_enhance, restore=not a.no_restore, face_det=a.face_det, pads=tuple(a.pads),
             nosmooth=a.nosmooth, face_det_batch_size=a.face_det_batch_size, landmarks=a.landmarks,
             stitch=a.stitch, up_face=a.up_face, without_rl1=a.without_rl1, precision=a.precision,
-            nms=a.nms, fps=a.fps, jpeg_decode=a.jpeg_decode, audio_load=a.audio_load)
+            nms=a.nms, fps=a.fps, jpeg_decode=a.jpeg_decode, audio_load=a.audio_load,
+            geometry=a.geometry)
     os.makedirs(os.path.dirname(os.path.abspath(a.outfile)), exist_ok=True)
     if a.outfile.lower().endswith(".avi"):
         video = r["enhanced"] if r["enhanced"] is not None else r["frames"]

@@ -62,6 +62,36 @@ def dnet_coefficients(semantic: np.ndarray, expression=None, one_shot: bool = Fa
     return out
 
 
+def dnet_coefficients_device(semantic_dev: torch.Tensor, expression=None, one_shot: bool = False, start: int = 0,
+                             stop: int | None = None) -> torch.Tensor:
+    """dnet_coefficients on the device (s2v_dnet_windows): ``semantic_dev`` float32 [N, 262] in device memory
+    -> float32 [stop - start, 73, 26] there, the same values.  ``expression``: (64,) array or tensor, host or
+    device.  The ratio's frame is the first whose expression and angle columns compare equal to the source's
+    (what find_crop_norm_ratio's argmin returns on rows without NaN), so no pass over the clip runs on the host
+    and nothing is copied back."""
+    from ._lib import check
+    if not (semantic_dev.is_cuda and semantic_dev.dtype == torch.float32 and semantic_dev.dim() == 2 and
+            semantic_dev.shape[1] == 262):
+        raise ops._lib.S2VError("dnet_coefficients_device: semantic must be a float32 [N, 262] HIP tensor")
+    sem = semantic_dev.contiguous()
+    N = sem.shape[0]
+    stop = N if stop is None else stop
+    if not 0 <= start <= stop <= N:
+        raise ValueError(f"dnet_coefficients_device: frames [{start}, {stop}) of {N}")
+    out = torch.empty((stop - start, 73, 26), dtype=torch.float32, device=sem.device)
+    if stop == start:
+        return out
+    exp = None
+    if expression is not None:
+        exp = torch.as_tensor(expression, dtype=torch.float32).reshape(-1)[:64].to(sem.device).contiguous()
+        if exp.numel() != 64:
+            raise ValueError("dnet_coefficients_device: expression holds 64 values")
+    ctx = audio._ctx(sem.device)
+    check(ctx.lib.s2v_dnet_windows(sem.data_ptr(), N, start, stop, None if exp is None else exp.data_ptr(),
+                                   1 if one_shot else 0, out.data_ptr(), ctx.stream), "s2v_dnet_windows")
+    return out
+
+
 def shard_range(n: int, rank: int, world: int):
     """Contiguous frame range of ``rank`` (sizes differ by at most one)."""
     base, extra = divmod(n, world)
