@@ -24,6 +24,7 @@ import torch
 from . import _lib, torch_ops
 from ._lib import (ACT_GELU_TANH, ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH,  # noqa: F401
                    IN_DIRECT, IN_NEAREST_UP2, IN_TRANSPOSED, PAD_REFLECT, PAD_ZERO, PREC_BF16X3, PREC_F16, PREC_F16X3, PREC_F32,
+                   TUNE_GLDS_TILE, TUNE_HALO_MIN_BLOCKS, TUNE_IN_FUSED, TUNE_RESIZE_UP2, TUNE_SMALLK_TILE, TUNE_X3_RATE_512,
                    check)
 
 F32 = 4
@@ -972,10 +973,6 @@ def split_act(ctx: Ctx, x: NHWC, out: NHWC | None = None) -> NHWC:
     S2V.split_act_(x.v, out.v, prec)
     out.split = prec
     return out
-
-
-(TUNE_HALO_MIN_BLOCKS, TUNE_GLDS_TILE, TUNE_SMALLK_TILE, TUNE_X3_RATE_512, TUNE_IN_FUSED,
- TUNE_RESIZE_UP2) = (0, 1, 2, 3, 4, 5)
 
 
 def tune(ctx: Ctx, key: int, value: int) -> int:

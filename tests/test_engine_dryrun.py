@@ -1,6 +1,6 @@
 """Dry run of every engine's host plan on CPU: the ``torch.ops.s2v`` launch ops and the libs2v
 entry points are replaced by no-ops that validate their arguments against the registered op
-schemas (count, tensor-ness, int lists) / the C ABI's argument counts, so the shape / view / slice
+schemas (count, tensor-ness, int lists) / the C ABI's argument counts and kinds, so the shape / view / slice
 bookkeeping of each forward (every NHWC assertion in ops.py) runs without a GPU.  Nothing is
 computed — numerics are the gpu-marked tests' job; this catches plumbing errors before a GPU box is
 spent on them."""
@@ -21,10 +21,15 @@ class _NoLib:
     def __getattr__(self, name):
         if name not in _lib.EXPORTS:
             raise AttributeError(name)
-        nargs = len(_lib._SIGS[name][1])
+        argtypes = _lib._SIGS[name][1]
 
         def fn(*args):
-            assert len(args) == nargs, f"{name}: {len(args)} args, ABI has {nargs}"
+            assert len(args) == len(argtypes), f"{name}: {len(args)} args, ABI has {len(argtypes)}"
+            for i, (a, t) in enumerate(zip(args, argtypes)):
+                try:
+                    t.from_param(a)                 # what the real foreign function does with each argument
+                except (TypeError, ctypes.ArgumentError) as e:
+                    raise AssertionError(f"{name}: argument {i} ({a!r}) is no {t.__name__}: {e}") from e
             self.calls[name] = self.calls.get(name, 0) + 1
             return 0
         return fn

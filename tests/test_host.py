@@ -57,18 +57,103 @@ def test_invalid_arguments_are_rejected_without_a_device():
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not available")
 def test_conv_params_struct_layout_matches_header(tmp_path):
+    """sizeof and the offset of every member, as the C compiler lays the header's struct out."""
+    P = _lib.ConvParams
+    names = [name for name, _ in P._fields_]
+    assert len(names) == 80 and {"ws", "x_bs", "res", "force_splits", "b_kn", "wt_scale"} <= set(names)
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\n'
-                   'int main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu\\n", sizeof(s2v_conv_params),'
-                   'offsetof(s2v_conv_params, ws), offsetof(s2v_conv_params, x_bs),'
-                   'offsetof(s2v_conv_params, res), offsetof(s2v_conv_params, force_splits),'
-                   'offsetof(s2v_conv_params, b_kn), offsetof(s2v_conv_params, wt_scale));return 0;}' % HEADER)
+                   'int main(){printf("%%zu\\n", sizeof(s2v_conv_params));\n%s\nreturn 0;}'
+                   % (HEADER, "\n".join('printf("%%zu\\n", offsetof(s2v_conv_params, %s));' % n for n in names)))
     exe = tmp_path / "sz"
     subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
     got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    P = _lib.ConvParams
-    assert got == [ctypes.sizeof(P), P.ws.offset, P.x_bs.offset, P.res.offset, P.force_splits.offset, P.b_kn.offset,
-                   P.wt_scale.offset]
+    assert got[0] == ctypes.sizeof(P)
+    assert dict(zip(names, got[1:], strict=True)) == {n: getattr(P, n).offset for n in names}
+
+
+def test_signatures_pinned_by_hand():
+    """One entry point per scalar kind, written out: what keeps a parser bug from passing silently."""
+    c_int, c_float, c_ll, vp = ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_void_p
+    P = ctypes.POINTER(_lib.ConvParams)
+    want = {
+        "s2v_conv2d_plan": (c_int, [P, vp]),
+        "s2v_tune": (c_int, [c_int, c_ll, vp]),
+        "s2v_gaussian_noise": (c_int, [vp, c_ll, ctypes.c_uint64, ctypes.c_uint64, vp]),
+        "s2v_face3d_align": (c_int, [vp, c_int, c_int, c_int, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp,
+                                     vp, vp, vp]),
+        "s2v_jpeg_ws_bytes": (ctypes.c_long, [c_int, c_int, c_int]),
+        "s2v_conv2d_ws_bytes": (ctypes.c_size_t, [P]),
+        "s2v_last_error": (ctypes.c_char_p, []),
+        "s2v_ffc_norm": (c_int, [vp, c_int, c_int, c_int, vp, vp, c_int, c_float, c_float, vp, vp, c_int,
+                                 c_float, c_int, c_float, vp, c_int, vp, c_int, vp, c_int, vp, c_int, vp]),
+    }
+    assert len(want["s2v_ffc_norm"][1]) == 24
+    for name, sig in want.items():
+        assert _lib._SIGS[name] == sig, name
+
+
+_MINI = """
+/* a comment with a prototype: int s2v_ghost(int a); */
+#ifndef MINI_H_
+#define MINI_H_
+#define S2V_MINI_MAX 7
+typedef void *s2v_stream_t;  // hipStream_t
+enum { S2V_A = 0, S2V_NEG = -3 };
+typedef struct s2v_mini {
+    const float *x; int n, h;   /* three members, two declarations */
+    const float *scale, *shift;
+    unsigned long long *stamps; size_t bytes;
+} s2v_mini;
+int s2v_count(void);
+const char *s2v_name(void);
+long s2v_run(const s2v_mini *p, const float *const *heads, long long n, double a, s2v_stream_t stream);
+#endif
+"""
+
+
+def test_parser_reads_what_the_header_uses():
+    consts, structs, sigs = _lib.parse_header(_MINI)
+    vp = ctypes.c_void_p
+    assert consts == {"S2V_MINI_MAX": 7, "S2V_A": 0, "S2V_NEG": -3}
+    assert structs == {"s2v_mini": [("x", vp), ("n", ctypes.c_int), ("h", ctypes.c_int), ("scale", vp), ("shift", vp),
+                                    ("stamps", vp), ("bytes", ctypes.c_size_t)]}
+    assert sigs == {"s2v_count": (ctypes.c_int, []), "s2v_name": (ctypes.c_char_p, []),
+                    "s2v_run": (ctypes.c_long, [vp, vp, ctypes.c_longlong, ctypes.c_double, vp])}
+    assert _lib.parse_header("int s2v_f(const s2v_conv_params *p);")[2] == {
+        "s2v_f": (ctypes.c_int, [ctypes.POINTER(_lib.ConvParams)])}
+
+
+@pytest.mark.parametrize("text,offending", [
+    ("int s2v_f(const float *x, short n);", "short"),                  # a type outside the table
+    ("enum { S2V_A = 0, S2V_B };", "S2V_B"),                           # an enumerator without a value
+    ("int s2v_f(const float *x, int out[11]);", "int out[11]"),        # an array parameter
+    ("int s2v_f(int a) __attribute__((pure));", "__attribute__"),      # a prototype the pattern does not consume
+    ("typedef struct s2v_t { int a[4]; } s2v_t;", "int a[4]"),
+    ("float *s2v_f(void);", "float *"),                                # a pointer return other than char *
+    ("#define S2V_N (1 << 3)", "(1 << 3)"),
+    ("int s2v_f(int a);\n}", "}"),                                     # text no declaration accounts for
+])
+def test_parser_refuses_what_it_does_not_know(text, offending):
+    with pytest.raises(_lib.S2VError, match=re.escape(offending)):
+        _lib.parse_header(text)
+
+
+def test_missing_header_is_named(tmp_path):
+    path = str(tmp_path / "include" / "s2v.h")
+    with pytest.raises(_lib.S2VError, match=re.escape(path)):
+        _lib._read_header(path)
+
+
+def test_binding_is_derived_from_the_header():
+    consts, structs, sigs = _lib.parse_header(open(HEADER).read())
+    assert sorted(sigs) == header_functions() and sigs == _lib._SIGS
+    assert structs["s2v_conv_params"] == _lib.ConvParams._fields_
+    assert all(getattr(_lib, k[len("S2V_"):]) == v for k, v in consts.items())
+    assert (_lib.ACT_GELU_TANH, _lib.PREC_F16, _lib.PCM_F64, _lib.E_WORKSPACE, _lib.DT_F64, _lib.TUNE_RESIZE_UP2,
+            _lib.CONV_GROUP_MAX) == (5, 3, 5, -3, 2, 5, 4)
+    from s2v_amd import ops
+    assert ops.TUNE_IN_FUSED == _lib.TUNE_IN_FUSED == 4
 
 
 @pytest.mark.parametrize("name,ctor", [("lnet", lambda: arch.LNetParams()),
